@@ -13,7 +13,13 @@ Workloads (BASELINE.json configs), selected with --config:
   4  Rico25    cond=unconditional  T=100  1024 layouts/GPU  sampling=random    (default at --gpus N>1: 8 GPUs = 8192)
 Random-init synthetic weights with the reference's init distributions (no checkpoints offline).
 
-The ONE JSON line carries the headline numerics mode (--precision, default `fast`) at top level and, at N=1:
+A plain run sets up, warms up, times the --steps steps of the headline workload and prints ONE JSON line: the headline
+numerics mode (--precision, default `fast`) at top level (`value`, `ms_per_step` = milliseconds of one timed step).
+`--dump-outputs DIR` also writes what the timed path returned in its last step (the final tokens, float32) as
+DIR/tokens.npy; the inputs are a function of the arguments alone, so two builds can be compared output for output.
+
+Everything else is measured only with `--full`: the roofline and per-kernel profile of the headline mode (one more
+eager pass), the decode timing, the live PMC traffic passes, the CPU baseline, and, at N=1:
   "modes"     every numerics mode on the headline workload, each with its own roofline against its own peak: exact (fp32
               MFMA, the mode of the bit-exact token tests), fast (fp16 operands / fp32 accumulate), and — config 2
               verbatim, i.e. GREEDY decoding — fast_verified (fast + exact re-decision of the near-tie layouts: the exact
@@ -101,7 +107,34 @@ def parse():
     ap.add_argument("--cpu-budget", type=float, default=22.0, help="seconds of CPU work for the cpu_baseline leg")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / shard / gather / report path only: gloo backend, fake sampler, no GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (roofline, decode, modes, configs, fid_features, "
+                         "layout_metrics, batch_shapes, weight_sensitivity, tokens_sha256, PMC traffic, cpu_baseline); "
+                         "the --modes / --no-* options above refine it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final tokens of the last timed step (float32) as DIR/tokens.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tokens):
+    """tokens: the (layouts, S) int32 host tensor the timed path returned in its last step.  Written as float32 (token ids are
+    exact below 2**24); above DUMP_MAX_BYTES a fixed, seeded sample of rows is written, with their indices in tokens_rows.npy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    t = tokens.numpy().astype(np.float32)
+    if t.nbytes > DUMP_MAX_BYTES:
+        n = (DUMP_MAX_BYTES - (1 << 20)) // (t.shape[1] * 4 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=n, replace=False))
+        t = t[rows]
+        np.save(os.path.join(out_dir, "tokens_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "tokens.npy"), t)
 
 
 # ----------------------------------------------------------------------------------------- self-spawn (N > 1)
@@ -192,6 +225,8 @@ def dry_run_main(a, world, rank, local_rank):
         dist.all_gather_object(allr, rates[0])
         rates, seen_world = allr, dist.get_world_size()
     assert final.shape[0] == n_global and torch.equal(final, _fake_tokens(0, n_global, a.warmup + a.steps - 1))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, final)
     sha = hashlib.sha256(sample_sharded(lambda f, c: _fake_tokens(f, c, SHA_SEED), max(SHA_LAYOUTS, world))
                          [:SHA_LAYOUTS].contiguous().numpy().tobytes()).hexdigest()
     if dist is not None:
@@ -451,10 +486,11 @@ HYBRID_KERNEL_SYMBOL = {"gemm_qkv_ln": "lngemm16x3_k<true, 2, false, 0, false, 2
 
 # ----------------------------------------------------------------------------------------- one workload, one mode
 def run_mode(a, spec, sd, precision, B, steps, warmup, cond_np, rank, world, local_rank, dist, with_roofline,
-             sampling=None, relation_graph=None, total=0, verified=False):
+             sampling=None, relation_graph=None, total=0, verified=False, outputs=None):
     """Times `steps` passes of one workload in one numerics mode.  B = this rank's layouts per step (weak scaling) or,
     with total > 0, the rank's shard of `total` (strong scaling).  cond_np: this rank's cond arrays (type c / refinement /
     relation) or None.  verified: greedy decoding through layout_dm_amd.verified (fast + exact re-decision).
+    outputs: a dict that receives "tokens", the gathered final tokens of the last timed step on the host.
     Returns (result dict, engine, last tokens)."""
     import torch
 
@@ -547,6 +583,8 @@ def run_mode(a, spec, sd, precision, B, steps, warmup, cond_np, rank, world, loc
         per_rank = {"min": round(float(allr.min()), 1), "max": round(float(allr.max()), 1), "ranks": int(allr.numel()),
                     "what": "layouts/s of each rank's own sampling launches (HIP events, no gather / barrier)"}
     fin = final.cpu()
+    if outputs is not None:
+        outputs["tokens"] = fin
     assert fin.shape[0] == n_global
     assert (fin != eng.mask_id).all(), "sampling left [MASK] tokens"
     if cond_np is not None:  # conditioned tokens survive (strong mask)
@@ -709,8 +747,11 @@ def main():
         cond_global = SP.synth_cond_c(spec, n_global, seed=0)
         cond_local = {"seq": cond_global["seq"][lo:hi], "mask": cond_global["mask"][lo:hi], "type": "c"}
 
+    outputs = {}
     res, eng, tokens = run_mode(a, spec, sd, a.precision, B, a.steps, a.warmup, cond_local, rank, world, local_rank,
-                                dist, with_roofline=not a.no_roofline, total=a.total)
+                                dist, with_roofline=a.full and not a.no_roofline, total=a.total, outputs=outputs)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outputs["tokens"])
     desc = eng.describe()
     per_gpu = f"{B}/GPU" if not a.total else f"{a.total} total ({B} on rank 0)"
     workload = (f"BASELINE config {config}: {a.dataset} cond={a.cond} T={a.timesteps} batch={per_gpu} "
@@ -755,7 +796,7 @@ def main():
         if k in res:
             out[k] = res[k]
 
-    if rank == 0:
+    if rank == 0 and a.full:
         # the reference's own timer (test.py:194-203) also covers ids -> {bbox,label,mask} and the copy to the host:
         # reported beside the headline (which stops at tokens resident in HBM), never folded into `value`
         reps = 20
@@ -773,6 +814,7 @@ def main():
 
     # every numerics mode in the one line (N=1): the bit-exact mode's throughput next to the headline's
     modes = a.modes if a.modes is not None else ("exact,split,mixed,hybrid,fast,fast_verified" if world == 1 else "")
+    modes = modes if a.full else ""
     modes = [m for m in modes.split(",") if m and m != "none"]
     if modes:
         out["modes"] = {}
@@ -838,7 +880,7 @@ def main():
         if v is not None:
             out[top_key] = v
             out["config"][top_key] = v
-    if world == 1 and not a.no_extras and not a.total and not a.batch:
+    if a.full and world == 1 and not a.no_extras and not a.total and not a.batch:
         out["configs"] = extras(a, SP, config, rank, world, local_rank, dist)
         out["fid_features"] = fid_timing(SP, local_rank)
         out["layout_metrics"] = layout_metrics_timing(local_rank)
@@ -853,13 +895,13 @@ def main():
             # engine on the same weights (a power-bound kernel's clock depends on operand statistics), which auto refuses
             # where its logits error is outside 1e-3
             out["weight_sensitivity"] = auto_on_trained_like(a, SP, spec, B, res["value"], rank, world, local_rank, dist)
-    if True:   # (r06: also with --no-extras — the one-rank RCCL test of the GPU suite compares it with the plain run's; one short call)
+    if a.full:   # (also with --no-extras — the one-rank RCCL test of the GPU suite compares it with the one-process run's; one short call)
         out["tokens_sha256"] = {"sha256": tokens_sha256(a, SP.synth_state_dict(SP.SPECS["rico25"], seed=0), SP.SPECS["rico25"],
                                                         rank, world, local_rank, dist),
                                 "of": f"first {SHA_LAYOUTS} layouts, Rico25 uncond random T={a.timesteps}, seed {SHA_SEED}, "
                                       f"precision {a.precision}; must not depend on n_gpus"}
 
-    if rank == 0 and world == 1 and not a.no_roofline and not a.no_traffic and "roofline" in out:
+    if a.full and rank == 0 and world == 1 and not a.no_roofline and not a.no_traffic and "roofline" in out:
         sym = KERNEL_SYMBOL.get(out["roofline"]["kernel"])
         if sym:
             vals, note = measure_traffic(sym, a.dataset, a.precision)
@@ -868,7 +910,7 @@ def main():
                 out["roofline"]["traffic_detail"] = traffic_detail(vals, note, out["roofline"]["kernel"], spec)
             else:
                 out["roofline"]["traffic_detail"] = {"source": f"live PMC collection unavailable: {note}"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(spec, sd, a.timesteps, a.sampling, cond_global, a.cpu_budget)
         out["config"]["cpu_baseline_kind"] = out["cpu_baseline"]["kind"]
         out["cpu_baseline_kind"] = out["cpu_baseline"]["kind"]

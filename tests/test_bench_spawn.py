@@ -36,3 +36,13 @@ def test_gpus_2_spawns_its_own_ranks_and_reports_once():
 def test_strong_scaling_ragged_shards():
     d = _run("--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--total", "37")
     assert d["scaling"] == "strong" and d["n_gpus"] == 2
+
+
+def test_dump_outputs_writes_the_last_steps_tokens(tmp_path):
+    import numpy as np
+
+    for d in ("a", "b"):
+        line = _run("--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d))
+        assert line["steps"] == 2
+    a, b = np.load(tmp_path / "a" / "tokens.npy"), np.load(tmp_path / "b" / "tokens.npy")
+    assert a.dtype == np.float32 and a.shape == (2048, 125) and np.array_equal(a, b)

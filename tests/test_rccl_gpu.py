@@ -16,7 +16,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--config", "4", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-traffic", "--modes", "none"]
+ARGS = ["--config", "4", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--no-traffic", "--modes", "none"]
 
 
 def _one_line(p):

@@ -7,7 +7,7 @@
 #
 #   suite [tag] [pytest args]      the GPU test suite (-m gpu)                                   -> pytest.log
 #   smoke [tag]                    __graft_entry__.smoke()                                       -> smoke.log
-#   bench [tag] [bench.py args]    the bench line (default: the driver's --steps 20 --warmup 2)  -> bench.json, bench.err
+#   bench [tag] [bench.py args]    the full bench line (bench.py --full; default --steps 20 --warmup 2)  -> bench.json, bench.err
 #   stats [tag] <precision>        rocprofv3 --kernel-trace --stats of a short bench.py run      -> rocprof_stats_<precision>.txt
 #   relstats [tag]                 the same for cond=relation (512 layouts, T = 100)             -> rocprof_stats_relation.txt
 #   sq [tag] <precision> <steps>   SQ / LDS / GRBM counter passes (tools/pmc_sq.sh)              -> sq_counters_<precision>.txt
@@ -25,7 +25,7 @@ Q="--no-extras --no-cpu-baseline --no-traffic --modes none"
 suite()    { timeout 1500 python -m pytest tests -m gpu -q "$@" > $O/pytest.log 2>&1; tail -3 $O/pytest.log; }
 smoke()    { timeout 400 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -2 $O/smoke.log; }
 bench()    { if [ $# -eq 0 ]; then set -- --steps 20 --warmup 2; fi
-             timeout 1500 python bench.py "$@" > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; tail -2 $O/bench.err; }
+             timeout 1500 python bench.py --full "$@" > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; tail -2 $O/bench.err; }
 stats()    { local p=${1:-fast}; local a="--precision $p --steps 2 --warmup 1"; [ "$p" = fast ] && a="--steps 3 --warmup 1"
              bash tools/rocprof_stats.sh $O/rocprof_stats_$p.txt $a $Q > /dev/null 2>&1; head -12 $O/rocprof_stats_$p.txt | cut -c1-200; }
 sq()       { bash tools/pmc_sq.sh $O/sq_counters_$1.txt $1 ${2:-4} > /dev/null 2>&1; head -30 $O/sq_counters_$1.txt; }
