@@ -238,6 +238,28 @@ int ldm_prdc(const float* d_real, int n_real, const float* d_fake, int n_fake, i
  * (parity to fp32 rounding).  Uses the current device; no handle.  Returns 0, -1 (bad argument) or -2 (launch failed). */
 int ldm_layout_metrics(const float* d_bbox, const uint8_t* d_mask, int B, int S, float* d_out6, void* stream);
 
+/* ---- average IoU, DocSim, Max-IoU (the IoU-family metrics of eval.py) --------------------------------------------------
+ * trainer/helpers/metric.py:300-507 (eval.py:173-176,211-215).  Device pointers in and out, no handle, the current device.
+ * box_f64 as in ldm_decode_layouts: 0 -> float32 boxes, 1 -> float64 (xc, yc, w, h), (rows, S, 4).  The compute type is
+ * double if any input is float64 (numpy's promotion); each box's l / t / r / b / area in its own dtype.  1 <= S <= 32.
+ * Returns 0, -1 (bad argument: nothing launched) or -2 (launch failed).  Results are float64. */
+/* per layout: d_out2 (B,2) = {average_iou-BLT, average_iou-VTN}; d_mask (B,S) uint8 (1 = element; any slots). */
+int ldm_eval_average_iou(const void* d_bbox, int box_f64, const uint8_t* d_mask, int B, int S, double* d_out2, void* stream);
+/* per pair b: DocSim of (layout b of set 1, layout b of set 2); d_n1 / d_n2 (B) int32 element counts, the elements first in
+ * their rows; d_label* (B,S) int64.  d_out (B).  *d_err (int32, zeroed by the call): bit 0 = a non-finite similarity. */
+int ldm_eval_docsim(const void* d_bbox1, int box1_f64, const int64_t* d_label1, const int32_t* d_n1, const void* d_bbox2,
+                    int box2_f64, const int64_t* d_label2, const int32_t* d_n2, int B, int S, double* d_out, int32_t* d_err,
+                    void* stream);
+/* Max-IoU pair scores of groups of layouts that share a label multiset, every layout's elements sorted stably by label:
+ * d_bbox1 (R1,S,4) + d_label1 (R1,S) int64, d_bbox2 (R2,S,4).  d_groups (G,6) int64 rows {first1, n1, first2, n2, n_elem,
+ * out_offset}, ordered by out_offset; group g fills d_out[out_offset + j * n1 + i] with the score of (set-1 row first1 + i,
+ * set-2 row first2 + j) (the reference's flat order), n_pairs = sum n1 * n2.  max_seg (<= S): the longest run of equal labels.
+ * *d_err (zeroed by the call): bit 0 = a NaN / infinite IoU (the reference raises there), bit 1 = a run longer than
+ * max_seg, bit 2 = a malformed group row. */
+int ldm_eval_max_iou_pairs(const void* d_bbox1, int box1_f64, const int64_t* d_label1, int R1, const void* d_bbox2, int box2_f64,
+                           int R2, int S, const int64_t* d_groups, int G, int64_t n_pairs, int max_seg, double* d_out,
+                           int32_t* d_err, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------- */
 /* average device time (ms) of the most recent ldm_sample_loop, measured with HIP events on the
  * stream it ran on; blocks until that loop has finished. */

@@ -31,6 +31,8 @@ EXPORTS = (
     # FID feature extractor (bound in layout_dm_amd/fid.py)
     "ldm_fid_create", "ldm_fid_destroy", "ldm_fid_last_error", "ldm_fid_load_weight", "ldm_fid_finalize",
     "ldm_fid_features", "ldm_prdc", "ldm_layout_metrics",
+    # average IoU / DocSim / Max-IoU (bound in layout_dm_amd/metrics.py)
+    "ldm_eval_average_iou", "ldm_eval_docsim", "ldm_eval_max_iou_pairs",
 )
 
 
@@ -124,6 +126,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_get_layout.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.ldm_describe.argtypes = [vp, C.c_char_p, i32]
     lib.ldm_layout_metrics.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.ldm_eval_average_iou.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+    lib.ldm_eval_docsim.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.ldm_eval_max_iou_pairs.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, C.c_int64, i32, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int

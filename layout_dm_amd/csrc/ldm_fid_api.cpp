@@ -232,3 +232,46 @@ extern "C" int ldm_layout_metrics(const float* d_bbox, const uint8_t* d_mask, in
   if (launch_layout_metrics(d_bbox, d_mask, B, S, d_out6, (hipStream_t)stream)) return -1;
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// ------------------------------------------------------------------------------------------ average IoU / DocSim / Max-IoU
+// (trainer/helpers/metric.py:300-507; kernels_eval_iou.hip).  Every argument is checked before anything is launched.
+static constexpr int kEvalMaxS = 32;
+
+extern "C" int ldm_eval_average_iou(const void* d_bbox, int box_f64, const uint8_t* d_mask, int B, int S, double* d_out2,
+                                    void* stream) {
+  if (B < 0 || S < 1 || S > kEvalMaxS || (box_f64 != 0 && box_f64 != 1)) return -1;
+  if (B == 0) return 0;
+  if (!d_bbox || !d_mask || !d_out2) return -1;
+  (void)hipGetLastError();
+  launch_eval_average_iou(d_bbox, box_f64, d_mask, B, S, d_out2, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int ldm_eval_docsim(const void* d_bbox1, int box1_f64, const int64_t* d_label1, const int32_t* d_n1,
+                               const void* d_bbox2, int box2_f64, const int64_t* d_label2, const int32_t* d_n2, int B, int S,
+                               double* d_out, int32_t* d_err, void* stream) {
+  if (B < 0 || S < 1 || S > kEvalMaxS || (box1_f64 != 0 && box1_f64 != 1) || (box2_f64 != 0 && box2_f64 != 1)) return -1;
+  if (!d_err) return -1;
+  (void)hipGetLastError();
+  if (hipMemsetAsync(d_err, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return -2;
+  if (B == 0) return 0;
+  if (!d_bbox1 || !d_label1 || !d_n1 || !d_bbox2 || !d_label2 || !d_n2 || !d_out) return -1;
+  launch_eval_docsim(d_bbox1, box1_f64, d_label1, d_n1, d_bbox2, box2_f64, d_label2, d_n2, B, S, d_out, d_err,
+                     (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int ldm_eval_max_iou_pairs(const void* d_bbox1, int box1_f64, const int64_t* d_label1, int R1, const void* d_bbox2,
+                                      int box2_f64, int R2, int S, const int64_t* d_groups, int G, int64_t n_pairs,
+                                      int max_seg, double* d_out, int32_t* d_err, void* stream) {
+  if (S < 1 || S > kEvalMaxS || G < 0 || n_pairs < 0 || R1 < 0 || R2 < 0 || max_seg < 1 || max_seg > S) return -1;
+  if ((box1_f64 != 0 && box1_f64 != 1) || (box2_f64 != 0 && box2_f64 != 1) || !d_err) return -1;
+  if (n_pairs > 0 && G == 0) return -1;
+  (void)hipGetLastError();
+  if (hipMemsetAsync(d_err, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return -2;
+  if (n_pairs == 0) return 0;
+  if (!d_bbox1 || !d_label1 || !d_bbox2 || !d_groups || !d_out) return -1;
+  launch_eval_max_iou(d_bbox1, box1_f64, d_label1, R1, d_bbox2, box2_f64, R2, S, d_groups, G, n_pairs, max_seg, d_out, d_err,
+                      (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}

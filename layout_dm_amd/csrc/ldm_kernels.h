@@ -193,6 +193,14 @@ void launch_stack_loop(const FusedLayerSet& ls, int F, int N, int B, int S, int 
 // alignment / overlap scores of decoded layouts (kernels_metrics.hip): bbox [B][S][4] f32, mask [B][S] u8 -> out [B][6];
 // -1 if S is outside [1, 256]
 int launch_layout_metrics(const float* bbox, const uint8_t* mask, int B, int S, float* out, hipStream_t st);
+// average IoU / DocSim / Max-IoU pair scores (kernels_eval_iou.hip); arguments checked by the C-ABI (ldm_fid_api.cpp)
+void launch_eval_average_iou(const void* bbox, int box_f64, const uint8_t* mask, int B, int S, double* out, hipStream_t st);
+void launch_eval_docsim(const void* bbox1, int box1_f64, const int64_t* label1, const int32_t* n1, const void* bbox2,
+                        int box2_f64, const int64_t* label2, const int32_t* n2, int B, int S, double* out, int32_t* err,
+                        hipStream_t st);
+void launch_eval_max_iou(const void* bbox1, int box1_f64, const int64_t* label1, int R1, const void* bbox2, int box2_f64, int R2,
+                         int S, const int64_t* groups, int G, int64_t n_pairs, int max_seg, double* out, int32_t* err,
+                         hipStream_t st);
 // ids -> {bbox, label, mask} (kernels_decode.hip); centres: [4][n_bin] f64 cluster centres or nullptr (linear bins)
 void launch_decode_layouts(const int32_t* tokens, int B, int E, int A, int n_category, int n_bin,
                            const double* centres, int box_f64, void* bbox, int64_t* label, uint8_t* mask,

@@ -8,11 +8,19 @@ Inputs are what `LayoutDM.sample` / `Engine.decode` return: `bbox` (B,S,4) (xc, 
 already on the device stay there (the decode kernel's output feeds the metrics kernel directly); CPU tensors are copied
 over.  One launch of `layout_metrics_k` (one wavefront per layout) computes all six scores; results come back as float32
 tensors on the input's device.  No CPU fallback: without the extension or a GPU this raises.
+
+The IoU-family metrics of eval.py (metric.py:300-507; eval.py:173-176,211-215) are here too, with the reference's names:
+
+    from layout_dm_amd.metrics import compute_average_iou, compute_maximum_iou, compute_docsim
+
+over lists of (bbox ndarray, label ndarray) layouts, plus tensor forms `average_iou(bbox, mask)` and
+`docsim(bbox_gt, label_gt, mask_gt, bbox_gen, label_gen, mask_gen)` for what Engine.decode leaves on the device.
 """
 from __future__ import annotations
 
 from typing import Dict
 
+import numpy as np
 import torch
 
 from .binding import _stream_ptr, load_library
@@ -55,3 +63,191 @@ def compute_alignment(bbox: torch.Tensor, mask: torch.Tensor) -> Dict[str, torch
 def compute_overlap(bbox: torch.Tensor, mask: torch.Tensor) -> Dict[str, torch.Tensor]:
     """helpers/metric.py:152-203."""
     return _as_dict(layout_metrics(bbox, mask), 3, bbox)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Average IoU, Max-IoU and DocSim (helpers/metric.py:300-507; eval.py:173-176,211-215): drop-ins with the reference's names,
+# signatures and return types over what test.py pickles, `layouts` = [(bbox ndarray (n,4) xc yc w h, label ndarray (n,))].
+# The kernels (kernels_eval_iou.hip) compute in float64 if a layout set is float64 (LayoutDM's kmeans decode) and in float32
+# otherwise (the dataset side), like numpy.  `disable_parallel` / `n_jobs` are accepted and ignored.  No CPU fallback.
+
+EVAL_MAX_ELEMENTS = 32   # elements per layout (the reference's datasets have <= 25)
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("layout_dm_amd.metrics needs a ROCm GPU (MI355X); there is no CPU path")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _set_dtype(layouts) -> np.dtype:
+    return np.dtype(np.float64) if any(np.asarray(b).dtype == np.float64 for b, _ in layouts) else np.dtype(np.float32)
+
+
+def _pack(layouts, S: int, dtype, order=None):
+    """(R,S,4) boxes, (R,S) int64 labels, (R,) int32 counts, elements first in their rows (sorted stably by label if order)"""
+    R = len(layouts)
+    box = np.zeros((R, S, 4), dtype)
+    lab = np.zeros((R, S), np.int64)
+    n = np.zeros(R, np.int32)
+    for r, (b, l) in enumerate(layouts):
+        b, l = np.asarray(b).reshape(-1, 4), np.asarray(l).reshape(-1)
+        if order:
+            o = np.argsort(l, kind="stable")
+            b, l = b[o], l[o]
+        k = len(l)
+        box[r, :k], lab[r, :k], n[r] = b, l, k
+    return box, lab, n
+
+
+def _check_elements(S: int):
+    if S > EVAL_MAX_ELEMENTS:
+        raise ValueError(f"at most {EVAL_MAX_ELEMENTS} elements per layout (got {S})")
+
+
+def average_iou(bbox: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """(B,2) float64 on the GPU: {BLT, VTN} average IoU of every layout (ldm_eval_average_iou).  bbox (B,S,4) float32 or
+    float64 (xc, yc, w, h) as Engine.decode / LayoutDM.sample leave them, mask (B,S) bool; device tensors stay there."""
+    dev = bbox.device if bbox.is_cuda else _device()
+    if bbox.dim() != 3 or bbox.shape[-1] != 4 or tuple(mask.shape) != tuple(bbox.shape[:2]):
+        raise ValueError(f"bbox must be (B,S,4) and mask (B,S); got {tuple(bbox.shape)}, {tuple(mask.shape)}")
+    f64 = bbox.dtype == torch.float64
+    b = bbox.to(device=dev, dtype=torch.float64 if f64 else torch.float32).contiguous()
+    m = mask.to(device=dev, dtype=torch.uint8).contiguous()
+    B, S = m.shape
+    _check_elements(S)
+    out = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        rc = lib.ldm_eval_average_iou(b.data_ptr(), int(f64), m.data_ptr(), B, max(S, 1), out.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"ldm_eval_average_iou failed ({rc})")
+    torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+def compute_average_iou(layouts, disable_parallel: bool = True, n_jobs=None) -> Dict[str, float]:
+    """helpers/metric.py:374-431."""
+    S = max([len(l) for _, l in layouts] + [1])
+    _check_elements(S)
+    box, _, n = _pack(layouts, S, _set_dtype(layouts))
+    mask = np.arange(S)[None, :] < n[:, None]
+    out = average_iou(torch.from_numpy(box), torch.from_numpy(mask)).cpu().numpy()
+    return {"average_iou-BLT": np.array(out[:, 0]).mean().item(), "average_iou-VTN": np.array(out[:, 1]).mean().item()}
+
+
+def _docsim_launch(dev, b1, l1, n1, b2, l2, n2) -> torch.Tensor:
+    B, S = l1.shape
+    _check_elements(S)
+    out = torch.zeros(B, dtype=torch.float64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        rc = lib.ldm_eval_docsim(b1.data_ptr(), int(b1.dtype == torch.float64), l1.data_ptr(), n1.data_ptr(), b2.data_ptr(),
+                                 int(b2.dtype == torch.float64), l2.data_ptr(), n2.data_ptr(), B, max(S, 1), out.data_ptr(),
+                                 err.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"ldm_eval_docsim failed ({rc})")
+    if int(err.item()) != 0:
+        raise ValueError("DocSim: the similarity matrix contains invalid numeric entries (NaN / inf boxes)")
+    return out
+
+
+def _compact(bbox: torch.Tensor, label: torch.Tensor, mask: torch.Tensor, dev):
+    """valid elements first in each row, in their order (a stable sort of ~mask on the device), + counts"""
+    m = mask.to(device=dev, dtype=torch.bool)
+    o = torch.sort((~m).to(torch.uint8), dim=1, stable=True).indices
+    b = torch.gather(bbox.to(dev), 1, o[..., None].expand(-1, -1, 4))
+    f64 = bbox.dtype == torch.float64
+    return (b.to(torch.float64 if f64 else torch.float32).contiguous(),
+            torch.gather(label.to(device=dev, dtype=torch.int64), 1, o).contiguous(), m.sum(1).to(torch.int32).contiguous())
+
+
+def docsim(bbox_gt, label_gt, mask_gt, bbox_gen, label_gen, mask_gen) -> torch.Tensor:
+    """(B,) float64 on the GPU: DocSim of every (gt[b], generated[b]) pair (ldm_eval_docsim), from padded tensors
+    (B,S,4) / (B,S) / (B,S) bool such as Engine.decode leaves them; both sides must have the same B and S."""
+    dev = bbox_gen.device if bbox_gen.is_cuda else _device()
+    if bbox_gt.shape != bbox_gen.shape or bbox_gt.dim() != 3 or bbox_gt.shape[-1] != 4:
+        raise ValueError(f"both sides must be (B,S,4); got {tuple(bbox_gt.shape)}, {tuple(bbox_gen.shape)}")
+    a, b = _compact(bbox_gt, label_gt, mask_gt, dev), _compact(bbox_gen, label_gen, mask_gen, dev)
+    return _docsim_launch(dev, a[0], a[1], a[2], b[0], b[1], b[2])
+
+
+def compute_docsim(layouts_gt, layouts_generated, disable_parallel: bool = True, n_jobs=None):
+    """helpers/metric.py:458-507: the mean over zip(layouts_gt, layouts_generated) of the per-pair DocSim (np.float64)."""
+    pairs = list(zip(layouts_gt, layouts_generated))
+    if not pairs:
+        return np.array([]).mean()
+    g, h = [p[0] for p in pairs], [p[1] for p in pairs]
+    S = max([len(l) for _, l in g + h] + [1])
+    _check_elements(S)
+    dev = _device()
+    b1, l1, n1 = (torch.from_numpy(x).to(dev) for x in _pack(g, S, _set_dtype(g)))
+    b2, l2, n2 = (torch.from_numpy(x).to(dev) for x in _pack(h, S, _set_dtype(h)))
+    return np.array(_docsim_launch(dev, b1, l1, n1, b2, l2, n2).cpu().numpy()).mean()
+
+
+def _groups(layouts):
+    g = {}
+    for i, (_, l) in enumerate(layouts):
+        g.setdefault(tuple(sorted(np.asarray(l).reshape(-1).tolist())), []).append(i)
+    return g
+
+
+def max_iou_pair_scores(layouts_1, layouts_2):
+    """Max-IoU pair scores of every group of layouts that share a label multiset, in ONE launch (ldm_eval_max_iou_pairs).
+    Returns [(key, n1, n2, scores (n1 * n2,) float64 in the reference's flat order: set-2 index outer)], groups ordered by
+    first appearance in layouts_1."""
+    g1, g2 = _groups(layouts_1), _groups(layouts_2)
+    keys = [k for k in g1 if k in g2]
+    if not keys:
+        return []
+    if any(len(k) == 0 for k in keys):
+        raise ZeroDivisionError("float division by zero")   # the reference divides by the element count of empty layouts
+    S = max(len(k) for k in keys)
+    _check_elements(S)
+    max_seg = max(max(np.unique(np.asarray(k), return_counts=True)[1]) for k in keys)
+    rows1 = [i for k in keys for i in g1[k]]
+    rows2 = [i for k in keys for i in g2[k]]
+    table, f1, f2, off = [], 0, 0, 0
+    for k in keys:
+        n1, n2 = len(g1[k]), len(g2[k])
+        table.append((f1, n1, f2, n2, len(k), off))
+        f1, f2, off = f1 + n1, f2 + n2, off + n1 * n2
+    dev = _device()
+    s1, s2 = [layouts_1[i] for i in rows1], [layouts_2[i] for i in rows2]
+    b1, l1, _ = _pack(s1, S, _set_dtype(s1), order=True)
+    b2, _, _ = _pack(s2, S, _set_dtype(s2), order=True)
+    b1, l1, b2 = (torch.from_numpy(x).to(dev) for x in (b1, l1, b2))
+    gt = torch.tensor(table, dtype=torch.int64, device=dev)
+    out = torch.empty(off, dtype=torch.float64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        rc = lib.ldm_eval_max_iou_pairs(b1.data_ptr(), int(b1.dtype == torch.float64), l1.data_ptr(), len(rows1), b2.data_ptr(),
+                                        int(b2.dtype == torch.float64), len(rows2), S, gt.data_ptr(), len(table), off,
+                                        int(max_seg), out.data_ptr(), err.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"ldm_eval_max_iou_pairs failed ({rc})")
+    e = int(err.item())
+    if e & 1:
+        raise ValueError("Max-IoU: an IoU matrix contains invalid numeric entries (NaN: two zero-area boxes)")
+    if e:
+        raise RuntimeError(f"ldm_eval_max_iou_pairs: device error flags {e}")
+    out = out.cpu().numpy()
+    return [(k, t[1], t[3], out[t[5]:t[5] + t[1] * t[3]]) for k, t in zip(keys, table)]
+
+
+def compute_maximum_iou(layouts_1, layouts_2, disable_parallel: bool = True, n_jobs=None) -> float:
+    """helpers/metric.py:317-371: pair scores on the device, each group's assignment by scipy on the host (as the reference)."""
+    from scipy.optimize import linear_sum_assignment
+
+    chosen = []
+    for _, n1, n2, s in max_iou_pair_scores(layouts_1, layouts_2):
+        scores = s.reshape(n1, n2)
+        ii, jj = linear_sum_assignment(scores, maximize=True)
+        chosen.append(scores[ii, jj])
+    if not chosen:
+        return 0.0
+    scores = np.concatenate(chosen)
+    return 0.0 if len(scores) == 0 else scores.mean().item()
