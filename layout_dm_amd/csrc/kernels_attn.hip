@@ -7,9 +7,6 @@
 // staged once in LDS (2 x 125 x 60 x 4 B = 60 KB), one query row per lane, two passes
 // (row max, then exp/accumulate) so the arithmetic has the same form as torch's softmax.
 // All lanes read the same K/V row => LDS broadcast reads (ds_read_b128, no bank conflicts).
-#include <cstdlib>
-#include <string>
-
 #include "ldm_kernels.h"
 
 namespace ldm {
@@ -422,17 +419,12 @@ static void launch_rows(const AttnArgs& a, hipStream_t st) {
 }
 
 void launch_attention(const AttnArgs& a, hipStream_t st) {
-  // LDM_ATTN32=rows selects the r01 VALU kernel for A/B timing
-  static const std::string attn32_knob = knob_env("LDM_ATTN32") ? knob_env("LDM_ATTN32") : "";
-  static const bool use_rows = attn32_knob == "rows";
-  static const bool use_staged = attn32_knob == "staged";  // A/B timing
-  // split mode: the fp16 x 3 kernel (LDM_ATTN32=direct keeps the fp32-MFMA kernel for A/B timing)
-  if (!a.in_f16 && a.out16 && a.out16lo && !a.out32 && attn32_knob.empty() &&
-      attention16x3_supported(a.S, a.dh, a.D, a.ld, a.ldo16)) {
+  // split mode: the fp16 x 3 kernel
+  if (!a.in_f16 && a.out16 && a.out16lo && !a.out32 && attention16x3_supported(a.S, a.dh, a.D, a.ld, a.ldo16)) {
     launch_attention16x3((const float*)a.qkv, a.out16, a.out16lo, a.B, a.S, a.H, a.dh, a.D, a.ld, a.ldo16, st);
     return;
   }
-  if (!a.in_f16 && !use_rows && !use_staged && a.S <= 128 && a.S > 96 && a.dh == 58 && a.D % 2 == 0 && a.ld % 2 == 0 &&
+  if (!a.in_f16 && a.S <= 128 && a.S > 96 && a.dh == 58 && a.D % 2 == 0 && a.ld % 2 == 0 &&
       a.ldo32 % 2 == 0 && a.ldo16 % 2 == 0) {
     constexpr int DH2 = 29;
     const size_t sh = (size_t)(128 * (2 * DH2 + 1)) * sizeof(float);
@@ -440,7 +432,7 @@ void launch_attention(const AttnArgs& a, hipStream_t st) {
                        a.out16lo, a.S, a.H, a.D, a.ld, a.ldo32, a.ldo16, 1.0f / sqrtf((float)a.dh));
     return;
   }
-  if (!a.in_f16 && !use_rows && a.S <= 128 && a.S > 96 && a.dh <= 58 && a.dh > 56) {
+  if (!a.in_f16 && a.S <= 128 && a.S > 96 && a.dh <= 58 && a.dh > 56) {
     constexpr int DH2 = 29;
     const size_t sh = (size_t)(128 * (2 * DH2 + 1) + 128 * 65 + 64) * sizeof(float);
     allow_big_lds((const void*)attn32_mfma_k<DH2>);

@@ -17,8 +17,6 @@
 //       D[i = d][j = query] gives each lane 4 consecutive d of its query: 8-byte stores.
 // K is staged in LDS with the XOR-swizzled 128-B-row image (conflict-free ds_read_b128), V is staged
 // transposed ([d][key], row stride 132 halfs -> conflict-free ds_read_b64).
-#include <cstdlib>
-
 #include "ldm_kernels.h"
 
 namespace ldm {
@@ -29,7 +27,8 @@ using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
 
 constexpr int VT_LD = 132;  // halfs per V^T row
 
-// ABL (timing ablations only): 0 = full kernel, 1 = no global loads, 2 = loads + QK^T only, 3 = no PV
+// ABL: 0 in the one instantiation (the timing ablations 1 = no global loads, 2 = loads + QK^T only, 3 = no PV were removed; the
+// parameter stays because profiles match the kernel's demangled name)
 template <int ABL>
 __global__ __launch_bounds__(256) void attn_mfma_k(const __half* __restrict__ qkv, __half* __restrict__ out, int S,
                                                    int H, int ldq, int ldo, float scale_log2e) {
@@ -407,9 +406,7 @@ void launch_attention16x3(const float* qkv, __half* out_hi, __half* out_lo, int 
 
 void launch_attention16(const __half* qkv, __half* out, int B, int S, int H, int dh, int ldq, int ldo, hipStream_t st) {
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)dh);
-  static const int abl = knob_int("LDM_ATTN_ABL", 0);  // (dev mode only: ldm_knobs.h)
-  auto kern = abl == 1 ? attn_mfma_k<1> : abl == 2 ? attn_mfma_k<2> : abl == 3 ? attn_mfma_k<3> : attn_mfma_k<0>;
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(256), 0, st, qkv, out, S, H, ldq, ldo, scale_log2e);
+  hipLaunchKernelGGL(attn_mfma_k<0>, dim3(B * H), dim3(256), 0, st, qkv, out, S, H, ldq, ldo, scale_log2e);
 }
 
 }  // namespace ldm

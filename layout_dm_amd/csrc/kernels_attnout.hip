@@ -201,7 +201,7 @@ __device__ __forceinline__ void ao_pv_pair(f32x16& o0, f32x16& o1, const f16x8& 
 
 // W2: two-product out_proj (Wo fp16 only: its lo half is neither read nor multiplied).  FFN (the hybrid mode): the block's plain-fp16 FFN runs on the
 // same accumulator tiles behind the attention — residual add in registers, LayerNorm-2, ldm_pipes.h FfnStream, ONE store of the block's output rows —
-// instead of the epilogue below and a launch of kernels_ffn16.hip: the attention block's output Q never reaches memory
+// instead of the epilogue below and an FFN launch of its own: the attention block's output Q never reaches memory
 template <bool TM, bool W2 = false, bool FFN = false>
 __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
   // (TM: cycles in the counted vmcnt waits [0..5] and in the barriers behind them [6..11] per sync site Ba Bb Bc Bd1 Bd2 Bd3, the

@@ -250,8 +250,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm16_k(const __half* __restrict
 // lane owns one output row — with a stage holding four images (A hi | W hi | A lo | W lo) and three MFMAs per fragment
 // pair on ONE accumulator (lo is unscaled: kSplitLoScale = 1, ldm_kernels.h; weights pre-scaled to magnitude ~1).  Why: gfx950's fp32 MFMA peaks at 157 TFLOP/s, its fp16 MFMA at 2 500: three
 // fp16 passes have a 5.3 x higher ceiling than one fp32 pass at the same (measured: better, 7e-7 vs 9e-7) logits error, and
-// 4 fragment reads feed 3 MFMAs instead of 2 feeding 1.  r03's split GEMM (gemm_f16_128x128<3>, register-staged, 221
-// layouts/s) was a numerics cross-check; this one makes the split mode the fast reference-precision mode.
+// 4 fragment reads feed 3 MFMAs instead of 2 feeding 1.  r03's register-staged split GEMM (221 layouts/s; since removed) was a
+// numerics cross-check; this one makes the split mode the fast reference-precision mode.
 struct Epi16x {
   const float* bias;
   const float* res;
@@ -354,11 +354,9 @@ __device__ __forceinline__ void x3_epilogue(const f32x16 (&acc)[TM][TN], const E
   }
 }
 
-// ABL (dev, tools/gemm_x3_probe.py): 0 the kernel; 1 no fragment reads / MFMAs (operand fills + barriers only); 2 no fills in the
-// steady state (fragment reads + MFMAs + barriers on whatever the prologue left in LDS); 3 MFMAs on constant fragments (fills +
-// MFMAs, no fragment reads).  Ablations produce wrong numbers by design and are reachable only through ldm_dev_bench_gemm_x3.
-// HINT (dev A/B, LDM_X3_CFG 10-12): bit 0 = the ACTIVATION fills carry the non-temporal policy (aux = 2: an operand that two column
-// tiles read and nobody else, straight from HBM / the Infinity Cache — FFN2's hidden activations, the out-projection's input).
+// ABL and HINT are 0 in every instantiation (the timing ablations and non-temporal activation fills they selected were measured and
+// removed); they stay in the parameter list because profiles and tests match the kernels' demangled names, as does the grp argument
+// (0: row-major tile order).
 template <int BM, int BN, int BK, int NSTAGE, int WM, int WN, int TAG, int ABL = 0, int HINT = 0>
 __global__ __launch_bounds__(WM* WN * 64) void gemm16x3_k(const __half* __restrict__ A, const __half* __restrict__ Alo,
                                                            const __half* __restrict__ W, const __half* __restrict__ Wlo,
@@ -462,233 +460,51 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm16x3_k(const __half* __restri
     asm volatile("" ::: "memory");
     if (ABL != 2 && kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1, (kt + NSTAGE - 1) % NSTAGE);
     const char* sbase = smem + (kt % NSTAGE) * STAGE_BYTES;
-    if constexpr (ABL == 1) continue;
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
       f16x8 a[TM], al[TM], w[TN], wl[TN];
 #pragma unroll
       for (int mi = 0; mi < TM; ++mi) {
-        if constexpr (ABL == 3) {
-          a[mi] = al[mi] = f16x8{(_Float16)0.5f, (_Float16)0.25f, (_Float16)0.125f, (_Float16)1.f, (_Float16)0.5f, (_Float16)0.25f, (_Float16)0.125f, (_Float16)1.f};
-          asm volatile("" : "+v"(a[mi]), "+v"(al[mi]));
-          continue;
-        }
         a[mi] = *reinterpret_cast<const f16x8*>(sbase + offA[ks] + mi * 32 * RB);
         al[mi] = *reinterpret_cast<const f16x8*>(sbase + HALF_BYTES + offA[ks] + mi * 32 * RB);
       }
 #pragma unroll
       for (int ni = 0; ni < TN; ++ni) {
-        if constexpr (ABL == 3) {
-          w[ni] = wl[ni] = f16x8{(_Float16)0.5f, (_Float16)0.25f, (_Float16)0.125f, (_Float16)1.f, (_Float16)0.5f, (_Float16)0.25f, (_Float16)0.125f, (_Float16)1.f};
-          asm volatile("" : "+v"(w[ni]), "+v"(wl[ni]));
-          continue;
-        }
         w[ni] = *reinterpret_cast<const f16x8*>(sbase + offW[ks] + ni * 32 * RB);
         wl[ni] = *reinterpret_cast<const f16x8*>(sbase + HALF_BYTES + offW[ks] + ni * 32 * RB);
       }
       // three passes over the wave's tiles — the small cross terms first, so that they meet the running sum before the big
       // term of this k step does — instead of three back-to-back MFMAs on one accumulator: consecutive MFMAs are independent
-      if constexpr (ABL != 4) {
 #pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
+      for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < TN; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ni], a[mi], acc[mi][ni], 0, 0, 0);
+        for (int ni = 0; ni < TN; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ni], a[mi], acc[mi][ni], 0, 0, 0);
 #pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
+      for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < TN; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], al[mi], acc[mi][ni], 0, 0, 0);
+        for (int ni = 0; ni < TN; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], al[mi], acc[mi][ni], 0, 0, 0);
 #pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
+      for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-          for (int ni = 0; ni < TN; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], a[mi], acc[mi][ni], 0, 0, 0);
-      } else {  // (dev A/B: the dependent order)
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < TN; ++ni) {
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ni], a[mi], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], al[mi], acc[mi][ni], 0, 0, 0);
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], a[mi], acc[mi][ni], 0, 0, 0);
-          }
-      }
+        for (int ni = 0; ni < TN; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], a[mi], acc[mi][ni], 0, 0, 0);
     }
   }
 
   x3_epilogue<BM, BN, WM, WN, TM, TN>(acc, e, m0, n0, wm, wn, frow, hi, smem, wave, lane);
 }
 
-// The same GEMM with the operands staged through REGISTERS (global_load_dwordx4 -> VGPRs -> ds_write_b128) instead of the LDS-DMA.
-// Why: the DMA path of the chip sustains ~6.4 TB/s (MI355X_MICROARCH.md "ldsdma-fill"), and gemm16x3_k sits on it — 5-6.5 TB/s of
-// operand fills, matrix pipes busy 0.28-0.36, half of the wave cycles in s_waitcnt (profiles/r04_call8_*) — while the vector
-// memory path reads the L2 at several times that.  Three-stage LDS ring, ONE register stage: iteration kt computes stage kt,
-// stores the registers (stage kt + 2, loaded during iteration kt - 1) and issues the loads of stage kt + 3.
-// BK = 32: a 64-byte row segment per (row, stage) = four 16-byte chunks; thread t owns chunk (t & 3) of rows (t >> 2) + i * NT / 4.
-template <int BM, int BN, int WM, int WN, int TAG>
-__global__ __launch_bounds__(WM* WN * 64) void gemm16x3r_k(const __half* __restrict__ A, const __half* __restrict__ Alo,
-                                                            const __half* __restrict__ W, const __half* __restrict__ Wlo,
-                                                            int lda, int ldw, int K, int tiles_n, Epi16x e) {
-  constexpr int BK = 32, NSTAGE = 3;
-  constexpr int NT = WM * WN * 64;
-  constexpr int RB = BK * 2;                       // 64 bytes per tile row
-  constexpr int HALF_BYTES = (BM + BN) * RB;       // [A rows | W rows] of one half (hi / lo)
-  constexpr int STAGE_BYTES = 2 * HALF_BYTES;
-  constexpr int RPP = NT / 4;                      // rows covered by one pass of the workgroup (4 chunks per row)
-  constexpr int NPA = BM / RPP, NPW = BN / RPP;    // passes over the A rows / W rows, per half
-  static_assert(BM % RPP == 0 && BN % RPP == 0, "tile rows must split evenly over the threads");
-  constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int tile = xcd_remap16(blockIdx.x, gridDim.x);
-  const int m0 = (tile / tiles_n) * BM;
-  const int n0 = (tile % tiles_n) * BN;
-
-  // ---- staging: global chunk (row r, chunk c) -> LDS slot r * RB + ((c ^ sw(r)) << 4), sw(r) = (r >> 2) & 3 (the read side below)
-  const int srow = tid >> 2, sc = tid & 3;
-  const __half* gA = A + (size_t)(m0 + srow) * lda + sc * 8;
-  const __half* gAl = Alo + (size_t)(m0 + srow) * lda + sc * 8;
-  const __half* gW = W + (size_t)(n0 + srow) * ldw + sc * 8;
-  const __half* gWl = Wlo + (size_t)(n0 + srow) * ldw + sc * 8;
-  static_assert(NPA >= 1 && NPA <= 2 && NPW >= 1 && NPW <= 2, "one or two passes per operand");
-  // (named registers, not arrays: hipcc keeps lambda-captured private arrays in scratch)
-  uint4 ra0, ra1, ral0, ral1, rw0, rw1, rwl0, rwl1;
-  ra1 = ral1 = rw1 = rwl1 = make_uint4(0, 0, 0, 0);
-  auto gload = [&](int kt) {
-    const size_t ko = (size_t)kt * BK;
-    ra0 = *reinterpret_cast<const uint4*>(gA + ko);
-    ral0 = *reinterpret_cast<const uint4*>(gAl + ko);
-    if constexpr (NPA > 1) {
-      ra1 = *reinterpret_cast<const uint4*>(gA + (size_t)RPP * lda + ko);
-      ral1 = *reinterpret_cast<const uint4*>(gAl + (size_t)RPP * lda + ko);
-    }
-    rw0 = *reinterpret_cast<const uint4*>(gW + ko);
-    rwl0 = *reinterpret_cast<const uint4*>(gWl + ko);
-    if constexpr (NPW > 1) {
-      rw1 = *reinterpret_cast<const uint4*>(gW + (size_t)RPP * ldw + ko);
-      rwl1 = *reinterpret_cast<const uint4*>(gWl + (size_t)RPP * ldw + ko);
-    }
-  };
-  const int soff0 = srow * RB + ((sc ^ ((srow >> 2) & 3)) << 4);                   // rows srow and srow + RPP share the
-  const int soff1 = (srow + RPP) * RB + ((sc ^ (((srow + RPP) >> 2) & 3)) << 4);   // swizzle when RPP % 16 == 0
-  auto sstore = [&](int stage) {
-    char* sb = smem + stage * STAGE_BYTES;
-    *reinterpret_cast<uint4*>(sb + soff0) = ra0;
-    *reinterpret_cast<uint4*>(sb + HALF_BYTES + soff0) = ral0;
-    if constexpr (NPA > 1) {
-      *reinterpret_cast<uint4*>(sb + soff1) = ra1;
-      *reinterpret_cast<uint4*>(sb + HALF_BYTES + soff1) = ral1;
-    }
-    *reinterpret_cast<uint4*>(sb + BM * RB + soff0) = rw0;
-    *reinterpret_cast<uint4*>(sb + HALF_BYTES + BM * RB + soff0) = rwl0;
-    if constexpr (NPW > 1) {
-      *reinterpret_cast<uint4*>(sb + BM * RB + soff1) = rw1;
-      *reinterpret_cast<uint4*>(sb + HALF_BYTES + BM * RB + soff1) = rwl1;
-    }
-  };
-
-  const int frow = lane & 31;
-  const int hi = lane >> 5;
-  const int fsw = (frow >> 2) & 3;
-  int offA[2], offW[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int phys = (ks * 2 + hi) ^ fsw;
-    offA[ks] = (wm * (BM / WM) + frow) * RB + phys * 16;
-    offW[ks] = BM * RB + (wn * (BN / WN) + frow) * RB + phys * 16;
-  }
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
-  const int nk = K / BK;
-  gload(0);
-  sstore(0);
-  if (nk > 1) { gload(1); sstore(1); }
-  if (nk > 2) gload(2);
-  auto mfmas = [&](const char* sbase, int ks) {
-    f16x8 a[TM], al[TM], w[TN], wl[TN];
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi) {
-      a[mi] = *reinterpret_cast<const f16x8*>(sbase + offA[ks] + mi * 32 * RB);
-      al[mi] = *reinterpret_cast<const f16x8*>(sbase + HALF_BYTES + offA[ks] + mi * 32 * RB);
-    }
-#pragma unroll
-    for (int ni = 0; ni < TN; ++ni) {
-      w[ni] = *reinterpret_cast<const f16x8*>(sbase + offW[ks] + ni * 32 * RB);
-      wl[ni] = *reinterpret_cast<const f16x8*>(sbase + HALF_BYTES + offW[ks] + ni * 32 * RB);
-    }
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < TN; ++ni) {
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[ni], a[mi], acc[mi][ni], 0, 0, 0);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], al[mi], acc[mi][ni], 0, 0, 0);
-        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[ni], a[mi], acc[mi][ni], 0, 0, 0);
-      }
-  };
-  for (int kt = 0; kt < nk; ++kt) {
-    __syncthreads();  // stage kt is visible; nobody reads stage kt - 1 (= the slot of stage kt + 2) any more
-    const char* sbase = smem + (kt % NSTAGE) * STAGE_BYTES;
-    mfmas(sbase, 0);
-    if (kt + 2 < nk) {
-      sstore((kt + 2) % NSTAGE);          // (the compiler waits for the loads of stage kt + 2 here: issued one iteration ago)
-      if (kt + 3 < nk) gload(kt + 3);
-    }
-    mfmas(sbase, 1);
-  }
-  x3_epilogue<BM, BN, WM, WN, TM, TN>(acc, e, m0, n0, wm, wn, frow, hi, smem, wave, lane);
-}
-
-template <int BM, int BN, int WM, int WN, int TAG>
-static void launch_x3r(const GemmArgs& g, hipStream_t st) {
-  const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-  Epi16x e{g.bias, g.res, g.C32, g.C16, g.C16lo, g.M, g.N, g.ldres, g.ldc32, g.ldc16, g.relu, g.out_scale > 0.f ? g.out_scale : 1.0f};
-  constexpr int lds = 3 * 2 * (BM + BN) * 32 * 2;
-  auto kern = gemm16x3r_k<BM, BN, WM, WN, TAG>;
-  allow_big_lds((const void*)kern);
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WM * WN * 64), lds, st, (const __half*)g.A, (const __half*)g.Alo,
-                     (const __half*)g.W, (const __half*)g.Wlo, g.lda, g.ldw, g.K, tiles_n, e);
-}
-
-template <int BM, int BN, int BK, int NSTAGE, int WM, int WN, int TAG, int ABL = 0, int HINT = 0>
+template <int BM, int BN, int BK, int NSTAGE, int WM, int WN, int TAG>
 static void launch_x3(const GemmArgs& g, hipStream_t st) {
   const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
   Epi16x e{g.bias, g.res, g.C32, g.C16, g.C16lo, g.M, g.N, g.ldres, g.ldc32, g.ldc16, g.relu, g.out_scale > 0.f ? g.out_scale : 1.0f};
   constexpr int lds = NSTAGE * 2 * (BM + BN) * BK * 2;
-  auto kern = gemm16x3_k<BM, BN, BK, NSTAGE, WM, WN, TAG, ABL, HINT>;
+  auto kern = gemm16x3_k<BM, BN, BK, NSTAGE, WM, WN, TAG>;
   allow_big_lds((const void*)kern);
-  static const int grp = knob_int("LDM_X3_GRP", 0);
   hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WM * WN * 64), lds, st, (const __half*)g.A, (const __half*)g.Alo,
-                     (const __half*)g.W, (const __half*)g.Wlo, g.lda, g.ldw, g.K, tiles_n, grp, e);
-}
-
-// dev: the production tile shape with an ablation (see gemm16x3_k)
-void launch_gemm16x3_abl(const GemmArgs& g, int abl, hipStream_t st) {
-  const int tiles_m = (g.M + 255) / 256, tiles_n = (g.N + 255) / 256;
-  Epi16x e{g.bias, g.res, g.C32, g.C16, g.C16lo, g.M, g.N, g.ldres, g.ldc32, g.ldc16, g.relu, g.out_scale > 0.f ? g.out_scale : 1.0f};
-  constexpr int lds = 2 * 2 * (256 + 256) * 32 * 2;
-  static const int grp = 0;
-#define LDM_X3_ABL(N_)                                                                                                   \
-  {                                                                                                                      \
-    auto kern = gemm16x3_k<256, 256, 32, 2, 2, 4, 6, N_>;                                                                \
-    allow_big_lds((const void*)kern);                                                                                    \
-    hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, (const __half*)g.A, (const __half*)g.Alo,      \
-                       (const __half*)g.W, (const __half*)g.Wlo, g.lda, g.ldw, g.K, tiles_n, grp, e);                    \
-  }
-  if (abl == 1) LDM_X3_ABL(1)
-  else if (abl == 2) LDM_X3_ABL(2)
-  else if (abl == 3) LDM_X3_ABL(3)
-  else LDM_X3_ABL(0)
-#undef LDM_X3_ABL
+                     (const __half*)g.W, (const __half*)g.Wlo, g.lda, g.ldw, g.K, tiles_n, 0, e);
 }
 
 // Split-mode GEMM.  Requires: K a multiple of 32 (the host pads: Dp / Fp), A / Alo with >= ceil(M / 256) * 256 rows and
@@ -700,24 +516,6 @@ void launch_gemm16x3(const GemmArgs& g, int tag, hipStream_t st) {
   // (profiles/r04_call6_* ... r04_call19_*): 128 x 128 606 layouts/s -> 256 x 128 706 -> coalesced epilogue 745 -> one
   // accumulator 754 -> 256 x 256 812; a 4-stage ring, 128 x 256, column-grouped tile orders, 128-byte operand rows (BK = 64),
   // operands through registers and the order of the three MFMAs change nothing or lose.
-  static const int cfg = knob_int("LDM_X3_CFG", 8);  // (dev: tile-shape A/B)
-  if (cfg == 0) { launch_x3<128, 128, 32, 3, 2, 2, 5>(g, st); return; }
-  if (cfg == 1) { launch_x3<128, 128, 32, 4, 2, 2, 5>(g, st); return; }
-  if (cfg == 2) { launch_x3<256, 128, 32, 3, 4, 2, 5>(g, st); return; }
-  if (cfg == 3) { launch_x3<128, 256, 32, 3, 2, 4, 5>(g, st); return; }
-  if (cfg == 5 && g.K % 64 == 0) { launch_x3<128, 128, 64, 2, 2, 2, 5>(g, st); return; }
-  if (cfg == 9) { launch_x3<256, 256, 32, 2, 2, 4, 5, 4>(g, st); return; }   // the dependent MFMA order (A/B)
-  if (cfg == 6) { launch_x3r<256, 128, 4, 2, 5>(g, st); return; }   // operands through registers
-  if (cfg == 7) { launch_x3r<128, 128, 2, 2, 5>(g, st); return; }
-  if (cfg == 10 || cfg == 11) {  // non-temporal activation fills: the two-reader operands (10), every GEMM (11)
-    switch (tag) {
-      case 0: if (cfg == 11) { launch_x3<256, 256, 32, 2, 2, 4, 0, 0, 1>(g, st); return; } break;
-      case 1: launch_x3<256, 256, 32, 2, 2, 4, 1, 0, 1>(g, st); return;
-      case 2: if (cfg == 11) { launch_x3<256, 256, 32, 2, 2, 4, 2, 0, 1>(g, st); return; } break;
-      case 3: launch_x3<256, 256, 32, 2, 2, 4, 3, 0, 1>(g, st); return;
-      default: break;
-    }
-  }
   switch (tag) {
     case 0: launch_x3<256, 256, 32, 2, 2, 4, 0>(g, st); return;
     case 1: launch_x3<256, 256, 32, 2, 2, 4, 1>(g, st); return;
@@ -727,7 +525,7 @@ void launch_gemm16x3(const GemmArgs& g, int tag, hipStream_t st) {
   }
 }
 
-template <int BM, int BN, int BK, int NSTAGE, int WM, int WN, int TAG = 0>
+template <int BM, int BN, int BK, int NSTAGE, int WM, int WN, int TAG>
 static void launch_cfg(const GemmArgs& g, hipStream_t st) {
   const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
   Epi16 e{g.bias, g.res, g.C32, g.C16, g.M, g.N, g.ldres, g.ldc32, g.ldc16, g.relu};
@@ -738,44 +536,15 @@ static void launch_cfg(const GemmArgs& g, hipStream_t st) {
                      (const __half*)g.W, g.lda, g.ldw, g.K, tiles_n, e);
 }
 
-// cfg ids are stable: used by the tuning hook (ldm_dev_bench_gemm) and the LDM_GEMM_CFG override
-int gemm16_block_n(int cfg) {
-  switch (cfg) {
-    case 2: case 3: return 128;
-    case 4: case 5: return 128;
-    case 6: return 256;
-    default: return 128;
-  }
-}
-int gemm16_block_k(int cfg) {
-  switch (cfg) {
-    case 1: case 3: case 5: case 6: case 7: case 8: return 64;
-    default: return 32;
-  }
-}
-
-void launch_gemm16(const GemmArgs& g, int cfg, int tag, hipStream_t st) {
-  if (cfg == 5) {  // production configuration: one symbol per Linear class
-    switch (tag) {
-      case 0: launch_cfg<128, 128, 64, 2, 2, 2, 0>(g, st); return;
-      case 1: launch_cfg<128, 128, 64, 2, 2, 2, 1>(g, st); return;
-      case 2: launch_cfg<128, 128, 64, 2, 2, 2, 2>(g, st); return;
-      case 3: launch_cfg<128, 128, 64, 2, 2, 2, 3>(g, st); return;
-      default: launch_cfg<128, 128, 64, 2, 2, 2, 4>(g, st); return;
-    }
-  }
-  switch (cfg) {
-    case 0: launch_cfg<128, 128, 32, 3, 2, 2>(g, st); break;
-    case 1: launch_cfg<128, 128, 64, 3, 2, 2>(g, st); break;
-    case 2: launch_cfg<128, 128, 32, 4, 2, 2>(g, st); break;
-    case 3: launch_cfg<256, 128, 64, 3, 4, 2>(g, st); break;
-    case 4: launch_cfg<256, 128, 32, 4, 4, 2>(g, st); break;
-    case 6: launch_cfg<256, 256, 64, 2, 4, 2>(g, st); break;
-    case 7: launch_cfg<256, 128, 64, 2, 4, 2>(g, st); break;
-    case 8: launch_cfg<128, 256, 64, 2, 2, 4>(g, st); break;
-    case 9: launch_cfg<256, 256, 32, 3, 4, 2>(g, st); break;
-    case 10: launch_cfg<256, 256, 32, 4, 4, 2>(g, st); break;
-    default: launch_cfg<128, 128, 32, 3, 2, 2>(g, st); break;
+// tag names the Linear class for rocprofv3 (0 qkv, 1 attn_out, 2 ffn1, 3 ffn2, 4 head): one symbol per class.  K % kGemm16BK == 0.
+void launch_gemm16(const GemmArgs& g, int tag, hipStream_t st) {
+  static_assert(kGemm16BK == 64, "the tile configuration below");
+  switch (tag) {
+    case 0: launch_cfg<128, 128, 64, 2, 2, 2, 0>(g, st); return;
+    case 1: launch_cfg<128, 128, 64, 2, 2, 2, 1>(g, st); return;
+    case 2: launch_cfg<128, 128, 64, 2, 2, 2, 2>(g, st); return;
+    case 3: launch_cfg<128, 128, 64, 2, 2, 2, 3>(g, st); return;
+    default: launch_cfg<128, 128, 64, 2, 2, 2, 4>(g, st); return;
   }
 }
 

@@ -893,28 +893,36 @@ int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st) {
               (!a.preAlo && npp != 1) || !a.pre_res || a.tokens ||
               (a.pre_panel_stride ? ((a.pre_panel_stride & 15) || a.pre_panel_stride < (size_t)a.M * 64) : (a.pre_lda < 32 * a.pre_astages || (a.pre_lda & 7)))))
     return -1;
-  // instantiations: <ADA, OUT, TM, ABL, PRE, NPM, NPP>; a launch without a GEMM prologue passes NPP = NPM (one instantiation per form)
+  // The 14 forms ldm_create can reach (tests/test_kernel_asm_lint.py counts them), as <ADA, OUT, PRE, NPM, NPP> with TM = false, ABL = 0.
+  // PRE: linear2 of the previous layer as the GEMM prologue of in_proj (from layer 1 on) and of the head, always but behind the fused FFN.
+  //   split   in_proj <1, 2, 0|1, 3, 3> (<1, 0, 0|1, 3, 3> under LDM_X3_ATTNOUT=0), linear1 <0, 1, 0, 3, 3>, head <0, 0, 1, 3, 3>          6
+  //   mixed   in_proj <1, 2, 0|1, 2, 2>, linear1 <0, 1, 0, 2, 2>, head <0, 0, 1, 2, 2>                                                   4
+  //   hybrid  FFN behind the attention (default): in_proj = mixed's layer-0 form, head <0, 0, 0, 1, 1>; two-launch FFN (LDM_HYB_FFN=0,
+  //           d_ff % 32 != 0): in_proj <1, 2, 1, 2, 1> from layer 1 on, linear1 <0, 3, 0, 1, 1>, head <0, 0, 1, 1, 1>                   4
   void (*kern)(LnGemmArgs) = nullptr;
-#define LG_PICK(NPM_, NPP_)                                                                                                                           \
-  kern = pre ? (panel ? lngemm16x3_k<true, 2, false, 0, true, NPM_, NPP_> : hi_only ? nullptr : half_out ? lngemm16x3_k<false, 1, false, 0, true, NPM_, NPP_> \
-                : a.ada ? lngemm16x3_k<true, 0, false, 0, true, NPM_, NPP_> : lngemm16x3_k<false, 0, false, 0, true, NPM_, NPP_>)                         \
-             : (panel ? lngemm16x3_k<true, 2, false, 0, false, NPM_, NPM_> : hi_only ? nullptr : half_out ? lngemm16x3_k<false, 1, false, 0, false, NPM_, NPM_> \
-                : a.ada ? lngemm16x3_k<true, 0, false, 0, false, NPM_, NPM_> : lngemm16x3_k<false, 0, false, 0, false, NPM_, NPM_>)
-  if (npm == 3 && npp == 3) LG_PICK(3, 3);
-  else if (npm == 2 && npp == 2) LG_PICK(2, 2);
-  // the hybrid mode's three forms beside mixed's in_proj: linear2 (plain fp16) in front of the two-product in_proj; linear1 in plain fp16 writing
-  // plain-fp16 hidden panels; linear2 + head in plain fp16
-  else if (npm == 2 && npp == 1 && pre && panel) kern = lngemm16x3_k<true, 2, false, 0, true, 2, 1>;
-  else if (npm == 1 && !pre && hi_only) kern = lngemm16x3_k<false, 3, false, 0, false, 1, 1>;
-  else if (npm == 1 && npp == 1 && pre && !half_out && !a.ada) kern = lngemm16x3_k<false, 0, false, 0, true, 1, 1>;
-  else if (npm == 1 && !pre && !half_out && !a.ada) kern = lngemm16x3_k<false, 0, false, 0, false, 1, 1>;   // the head alone (behind the fused fp16 FFN)
-#undef LG_PICK
+  const bool ffn1 = half_out && !panel && !hi_only && !pre;   // linear1 + ReLU, hi / lo rows or panels (OUT = 1)
+  const bool head = !half_out && !a.ada;
+  if (npm == 3 && npp == 3) {
+    if (panel) kern = pre ? lngemm16x3_k<true, 2, false, 0, true, 3, 3> : lngemm16x3_k<true, 2, false, 0, false, 3, 3>;
+    else if (!half_out && a.ada) kern = pre ? lngemm16x3_k<true, 0, false, 0, true, 3, 3> : lngemm16x3_k<true, 0, false, 0, false, 3, 3>;
+    else if (ffn1) kern = lngemm16x3_k<false, 1, false, 0, false, 3, 3>;
+    else if (head && pre) kern = lngemm16x3_k<false, 0, false, 0, true, 3, 3>;
+  } else if (npm == 2 && npp == 2) {
+    if (panel) kern = pre ? lngemm16x3_k<true, 2, false, 0, true, 2, 2> : lngemm16x3_k<true, 2, false, 0, false, 2, 2>;
+    else if (ffn1) kern = lngemm16x3_k<false, 1, false, 0, false, 2, 2>;
+    else if (head && pre) kern = lngemm16x3_k<false, 0, false, 0, true, 2, 2>;
+  } else if (npm == 2 && npp == 1) {
+    if (panel && pre) kern = lngemm16x3_k<true, 2, false, 0, true, 2, 1>;
+  } else if (npm == 1 && npp == 1) {
+    if (hi_only && !pre) kern = lngemm16x3_k<false, 3, false, 0, false, 1, 1>;
+    else if (head) kern = pre ? lngemm16x3_k<false, 0, false, 0, true, 1, 1> : lngemm16x3_k<false, 0, false, 0, false, 1, 1>;
+  }
   if (!kern) return -1;
-  if (tm && !pre && !panel && !hi_only && npm == 3) kern = half_out ? lngemm16x3_k<false, 1, true> : a.ada ? lngemm16x3_k<true, 0, true> : lngemm16x3_k<false, 0, true>;
+  if (tm && npm == 3 && !pre && !panel) kern = a.ada ? lngemm16x3_k<true, 0, true> : lngemm16x3_k<false, 1, true>;   // (in_proj under LDM_X3_ATTNOUT=0, linear1)
 #ifdef LDM_LNGEMM_ABL_BUILD   // measurement build (tools/build_measurement_variants.py lngemm): compile-time timing variants of the loop
   static const int abl_knob = (int)knob_int("LDM_LNGEMM_ABL", 0);
   const int abl = (pre || panel || hi_only || npm != 3) ? 0 : abl_knob;
-#define LG_ABL(n) case n: kern = half_out ? lngemm16x3_k<false, 1, false, n> : a.ada ? lngemm16x3_k<true, 0, false, n> : lngemm16x3_k<false, 0, false, n>; break;
+#define LG_ABL(n) case n: kern = a.ada ? lngemm16x3_k<true, 0, false, n> : lngemm16x3_k<false, 1, false, n>; break;
   switch (abl) { LG_ABL(2) LG_ABL(4) LG_ABL(8) LG_ABL(6) LG_ABL(10) LG_ABL(12) LG_ABL(14) LG_ABL(16) LG_ABL(32) LG_ABL(64) default: break; }
 #undef LG_ABL
 #endif

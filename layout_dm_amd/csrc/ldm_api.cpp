@@ -148,10 +148,6 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     h->Fq = round_up(h->F, 64);
     h->Mpad = round_up((int)Mc, 256);
     const size_t Mp = h->Mpad;
-    const char* env = knob_env("LDM_GEMM_CFG");  // "q,o,1,2,h" tile-config ids (tuning override)
-    int defaults[5] = {5, 5, 5, 5, 5};
-    for (int i = 0; i < 5; ++i) h->gemm_cfg[i] = defaults[i];
-    if (env) sscanf(env, "%d,%d,%d,%d,%d", &h->gemm_cfg[0], &h->gemm_cfg[1], &h->gemm_cfg[2], &h->gemm_cfg[3], &h->gemm_cfg[4]);
     if (const char* fa = knob_env("LDM_FUSED_ATTN")) h->fused_attn = atoi(fa) == 0 ? 0 : 6;
     if (const char* sp = knob_env("LDM_STACK_LOOP")) h->stack_loop = atoi(sp);
     h->rel_loop = knob_int("LDM_REL_LOOP", 1);
@@ -206,28 +202,21 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     h->lngemm = h->D == 464 && h->Dp == 512 && (3 * h->D) % 4 == 0 && h->F % 4 == 0 && h->x3_qkv_tiles * 32 <= 2048 &&
                 h->x3_ffn1_tiles * 32 <= 2048 && h->x3_head_tiles * 32 <= 2048 && h->x3_qkv_tiles * 32 <= round_up(3 * h->D, 256) &&
                 h->x3_ffn1_tiles * 32 <= round_up(h->F, 256) && h->x3_head_tiles * 32 <= round_up(h->C, 256) &&
-                knob_int("LDM_X3_LNGEMM", 4) != 0;
-    // The two N = d_model GEMMs can run as the GEMM PROLOGUE of the row-resident kernel that normalises their sum (kernels_lngemm.hip PRE)
-    // instead of as gemm16x3_k launches.  Default (level 4): linear2 only — the fused launch is 28 us per layer cheaper than the two it
-    // replaces, +4 % whole-job same-box.  Fusing out_proj as well (LDM_DEV=1 LDM_X3_LNGEMM=2; 3 = out_proj only) saves nothing per launch
-    // and costs the overlap between the two chunk pipelines (a fused launch fills every CU alone): -5 % (profiles/r05_call24_31_*).
-    // LDM_X3_LNGEMM=1: no prologue (the first r05 structure).  The K-slab weight images are only built for what is selected.
-    const int lv = (int)knob_int("LDM_X3_LNGEMM", 4);
-    h->lngemm_pre = h->lngemm && h->Dp % 32 == 0 && h->Fp % 32 == 0 && h->D <= 480 && lv >= 2;
-    h->pre_out = h->lngemm_pre && (lv == 2 || lv == 3);
-    h->pre_ffn2 = h->lngemm_pre && (lv == 2 || lv == 4);
+                knob_int("LDM_X3_LNGEMM", 1) != 0;
+    // linear2 runs as the GEMM PROLOGUE of the row-resident kernel that normalises its sum (kernels_lngemm.hip PRE: the next layer's AdaLN +
+    // in_proj, or the head) instead of as a gemm16x3_k launch: 28 us per layer cheaper than the two launches it replaces, +4 % whole-job
+    // same-box.  Fusing out_proj the same way saved nothing per launch and cost the overlap between the two chunk pipelines (a fused launch
+    // fills every CU alone): -5 % (profiles/r05_call24_31_*); the attention + out_proj launch below replaced it.
+    h->hid_panels = h->lngemm && h->panel_rows <= (size_t)round_up((int)Mc, 256) + 64 && knob_int("LDM_X3_HIDPANEL", 1) != 0;
     // r06: attention + out_proj as one layout-resident launch behind an in_proj that writes hi / lo panels (kernels_attnout.hip);
     // LDM_DEV=1 LDM_X3_ATTNOUT=0: attn16x3_k + the out_proj launch of gemm16x3_k (the r05 structure)
-    h->hid_panels = h->lngemm && h->pre_ffn2 && h->Fp % 32 == 0 && h->panel_rows <= (size_t)round_up((int)Mc, 256) + 64 &&
-                    knob_int("LDM_X3_HIDPANEL", 1) != 0;
-    h->attnout = h->lngemm && !h->pre_out && h->qkvp_hi && h->panel_rows * 64 * 2 < (1ull << 32) && knob_int("LDM_X3_ATTNOUT", 1) != 0;
+    h->attnout = h->lngemm && h->qkvp_hi && h->panel_rows * 64 * 2 < (1ull << 32) && knob_int("LDM_X3_ATTNOUT", 1) != 0;
     h->mixed = mixed;
-    h->w2p = h->lngemm && h->pre_ffn2 && h->attnout && mixed && (mixed == 1 || h->hid_panels);
+    h->w2p = h->lngemm && h->attnout && mixed && (mixed == 1 || h->hid_panels);
     if (h->w2p) {
       h->np_w = 2;
       h->np_ffn = mixed == 2 ? 1 : 2;
       h->ffn_fused = mixed == 2 && h->F % 32 == 0 && h->F <= 2048 && knob_int("LDM_HYB_FFN", 1) != 0;
-      h->attn_ffn_fused = h->ffn_fused && knob_int("LDM_HYB_ATTNFFN", 1) != 0;
     }
     if (mixed && !h->w2p) {
       h->err = "precision mixed / hybrid: only the reference backbone's geometry (d_model 464, 8 heads, <= 128 tokens per layout) has the two-product kernels; use precision split";
@@ -448,8 +437,8 @@ extern "C" int ldm_describe(const ldm_handle* h, char* buf, int cap) {
   if (h->cfg.precision != LDM_PREC_FAST_F16) {
     kern = "tiled_gemm+attn";
     if (h->lngemm)
-      kern = std::string("row_resident_ln_gemm") + (h->attn_ffn_fused ? "+attn_ffn_fused_fp16" : h->ffn_fused ? "+ffn_fused_fp16" : h->pre_ffn2 ? "+linear2_prologue" : "") + (h->pre_out ? "+out_proj_prologue" : "") +
-             (h->attnout ? "+attn_out_proj_fused" : h->pre_ffn2 && h->pre_out ? "+attn" : "+tiled_gemm+attn");
+      kern = std::string("row_resident_ln_gemm") + (h->ffn_fused ? "+attn_ffn_fused_fp16" : "+linear2_prologue") +
+             (h->attnout ? "+attn_out_proj_fused" : "+tiled_gemm+attn");
   }
   s += ";kernels=" + kern;
   s += std::string(";loop=") + (loop ? "one_launch" : "per_step_graph");

@@ -50,10 +50,9 @@ static int denoise_chunk_fast(ldm_handle* h, const int32_t* d_tokens, int t, int
     GemmArgs g{};
     g.A = A; g.W = W; g.bias = bias; g.relu = relu; g.res = res; g.ldres = D;
     g.C32 = C32; g.ldc32 = ldc32; g.C16 = C16; g.ldc16 = ldc16;
-    const int cfg = h->gemm_cfg[tag];
-    g.M = M; g.N = N; g.K = round_up(K, gemm16_block_k(cfg)); g.lda = lda; g.ldw = ldw; g.precision = 1;
+    g.M = M; g.N = N; g.K = round_up(K, kGemm16BK); g.lda = lda; g.ldw = ldw; g.precision = 1;
     ldm_handle::Scope sc(h, st, name, flops, bytes);
-    launch_gemm16(g, cfg, tag, st);
+    launch_gemm16(g, tag, st);
   };
   for (int i = 0; i < h->L; ++i) {
     const LayerW& w = h->layers[i];
@@ -100,19 +99,22 @@ static int denoise_chunk_fast(ldm_handle* h, const int32_t* d_tokens, int t, int
 }
 
 // denoiser forward for `Bc` layouts whose tokens start at d_tokens -> h->logits [Bc*S, Cp]
-// exact: fp32 MFMA tiles; split: the fp16 x 3 LDS-DMA GEMM (kernels_gemm16.hip gemm16x3_k; LDM_DEV=1 LDM_SPLIT_GEMM=old: the
-// register-staged r03 kernel, kept as a cross-check)
-static void launch_gemm_mode(const GemmArgs& g, int tag, hipStream_t st) {
-  static const bool old_split = knob_env("LDM_SPLIT_GEMM") && std::string(knob_env("LDM_SPLIT_GEMM")) == "old";
-  if (g.precision == LDM_PREC_SPLIT_F16 && !old_split && g.K % 32 == 0) launch_gemm16x3(g, tag, st);
-  else launch_gemm(g, st);
+// exact: fp32 MFMA tiles; split: the fp16 x 3 LDS-DMA GEMM (kernels_gemm16.hip gemm16x3_k)
+static int launch_gemm_mode(ldm_handle* h, const GemmArgs& g, int tag, hipStream_t st) {
+  if (g.precision != LDM_PREC_SPLIT_F16) {
+    launch_gemm(g, st);
+    return 0;
+  }
+  if (g.K % 32) return h->fail(-4, "split GEMM: K = %d is not a multiple of 32", g.K);   // (Dp / Fp are multiples of 64)
+  launch_gemm16x3(g, tag, st);
+  return 0;
 }
 
-// lngemm level 2: linear2 of layer `w` (+ bias + the residual Q) as the GEMM prologue of the launch that normalises its sum
+// linear2 of layer `w` (+ bias + the residual Q) as the GEMM prologue of the launch that normalises its sum
 static void ffn2_prologue(ldm_handle* h, const LayerW& w, LnGemmArgs& a) {
   a.preA = h->hid16; a.preAlo = h->hid16lo; a.pre_lda = h->Fp; a.pre_astages = h->Fp / 32; a.pre_stages = ldm_pack::x3_slab_stages(h->Fp);
   a.pre_img = (const char*)w.x3_ffn2_slab; a.pre_bias = w.b2; a.pre_scale = w.s2;
-  a.pre_res = h->Q; a.pre_out = nullptr;
+  a.pre_res = h->Q;
   a.pre_panel_stride = h->hid_panels ? h->panel_rows * 64 : 0;
   a.np_pre = h->np_ffn;
   if (h->np_ffn == 1) a.preAlo = nullptr;   // (plain-fp16 hidden activations: linear1 wrote no lo panels)
@@ -146,7 +148,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
         a.bias = w.b_in; a.N = 3 * D;
         a.C32 = h->qkv32; a.ldc32 = 3 * D;
       }
-      const bool pre = h->pre_ffn2 && !h->ffn_fused && i > 0;   // x = Q + hid · W2^T + b2 of the PREVIOUS layer, computed in this launch (never stored)
+      const bool pre = !h->ffn_fused && i > 0;   // x = Q + hid · W2^T + b2 of the PREVIOUS layer, computed in this launch (never stored)
       if (pre) ffn2_prologue(h, h->layers[i - 1], a);
       ldm_handle::Scope sc(h, st, pre ? "gemm_ffn2_qkv_ln" : "gemm_qkv_ln", gemm_flops(M, 3 * D, D) + (pre ? gemm_flops(M, D, F) : 0.0),
                            (double)M * D * 8 + (double)M * 3 * D * 4 + (pre ? (double)M * F * 4 : 0.0));
@@ -179,7 +181,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
         g.M = M; g.N = 3 * D; g.K = f16 ? Dp : D; g.lda = f16 ? Dp : D; g.ldw = f16 ? Dp : D;
         g.ldc32 = 3 * D; g.ldc16 = 3 * D; g.precision = prec;
         ldm_handle::Scope sc(h, st, "gemm_qkv", gemm_flops(M, 3 * D, D), (double)M * D * esz + (double)M * 3 * D * (prec == 1 ? 2 : 4));
-        launch_gemm_mode(g, 0, st);
+        if (int rc = launch_gemm_mode(h, g, 0, st)) return rc;
       }
     }
     if (split && h->attnout) {  // attention + out-proj + residual in ONE layout-resident launch:  Q = P + softmax(q k^T) v · Wo^T + bo
@@ -188,12 +190,12 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
       a.w_img = (const char*)w.x3_out_kstep;
       a.res = h->P; a.bias = w.b_out; a.out = h->Q;
       a.S = h->S; a.D = D; a.scale = 1.0f / sqrtf((float)h->dh); a.out_scale = w.s_out; a.w2 = h->w2p;
-      if (h->attn_ffn_fused) {   // hybrid: the block's plain-fp16 FFN behind the attention in the same launch; P receives x + attention + FFN
+      if (h->ffn_fused) {   // hybrid: the block's plain-fp16 FFN behind the attention in the same launch; P receives x + attention + FFN
         a.ffn_img = (const char*)w.ffn16_img; a.ffn_gamma = w.g2; a.ffn_beta = w.be2; a.ffn_b1 = w.b1; a.ffn_b2 = w.b2;
         a.ffn_out = h->P; a.F = F; a.n_chunks = F / 32;
       }
-      ldm_handle::Scope sc(h, st, h->attn_ffn_fused ? "attn_out_ffn_fused" : "attn_out_fused",
-                           4.0 * Bc * h->H * (double)h->S * h->S * h->dh + gemm_flops(M, D, D) + (h->attn_ffn_fused ? gemm_flops(M, F, D) + gemm_flops(M, D, F) : 0.0),
+      ldm_handle::Scope sc(h, st, h->ffn_fused ? "attn_out_ffn_fused" : "attn_out_fused",
+                           4.0 * Bc * h->H * (double)h->S * h->S * h->dh + gemm_flops(M, D, D) + (h->ffn_fused ? gemm_flops(M, F, D) + gemm_flops(M, D, F) : 0.0),
                            (double)M * 3 * h->H * 64 * 4 + (double)M * D * 8);
       if (launch_attnout16x3(a, Bc, st)) return h->fail(-4, "fused attention + out_proj: geometry not supported");
     } else {
@@ -209,7 +211,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
                            (double)M * 3 * D * (a.in_f16 ? 2 : 4) + (double)M * D * esz);
       launch_attention(a, st);
     }
-    if (!(split && h->pre_out)) {  // out-proj + residual onto the normed x:  Q = P + att·Wo^T + bo
+    {  // out-proj + residual onto the normed x:  Q = P + att·Wo^T + bo
       GemmArgs g{};
       g.A = f16 ? (const void*)h->att16 : (const void*)h->att32;
       g.Alo = h->att16lo;
@@ -220,19 +222,11 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
       g.C32 = h->Q; g.ldc32 = D;
       g.M = M; g.N = D; g.K = f16 ? Dp : D; g.lda = f16 ? Dp : D; g.ldw = f16 ? Dp : D; g.precision = prec;
       ldm_handle::Scope sc(h, st, "gemm_attn_out", gemm_flops(M, D, D), (double)M * D * (esz + 8));
-      launch_gemm_mode(g, 1, st);
+      if (int rc = launch_gemm_mode(h, g, 1, st)) return rc;
     }
     }
-    if (split && h->attn_ffn_fused) {
+    if (split && h->ffn_fused) {
       // (the FFN ran behind the attention: kernels_attnout.hip FFN)
-    } else if (split && h->ffn_fused) {   // hybrid: P = Q + b2 + W2 relu(W1 LN2(Q) + b1) in ONE plain-fp16 launch (kernels_ffn16.hip); the hidden activations stay on chip
-      FfnRowsArgs a{};
-      a.x = h->Q; a.out = h->P;
-      a.gamma = w.g2; a.beta = w.be2; a.b1 = w.b1; a.b2 = w.b2;
-      a.img = (const char*)w.ffn16_img;
-      a.M = M; a.D = D; a.F = F; a.n_chunks = F / 32;
-      ldm_handle::Scope sc(h, st, "ffn_fused16", gemm_flops(M, F, D) + gemm_flops(M, D, F), (double)M * D * 8);
-      if (launch_ffn16_rows(a, st)) return h->fail(-4, "fused fp16 FFN: geometry not supported");
     } else if (split && h->lngemm) {  // LayerNorm 2 + FFN1 + ReLU in ONE row-resident launch: hi / lo hidden activations out
       LnGemmArgs a{};
       a.x = h->Q; a.ldx = D;
@@ -243,13 +237,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
       if (h->hid_panels) { a.panel_out = 1; a.panel_stride = h->panel_rows * 64; }   // (read back by ffn2_prologue in the same form)
       a.M = M; a.N = F; a.D = D; a.S = h->S; a.np_main = h->np_ffn;
       if (h->np_ffn == 1) a.C16lo = nullptr;   // hybrid: ReLU output rounded once (panel-major: ldm_create requires hid_panels for it)
-      if (h->pre_out) {   // Q = P + att · Wo^T + bo computed in this launch, written once (linear2's residual base)
-        a.preA = h->att16; a.preAlo = h->att16lo; a.pre_lda = Dp; a.pre_astages = Dp / 32; a.pre_stages = ldm_pack::x3_slab_stages(Dp);
-        a.pre_img = (const char*)w.x3_out_slab; a.pre_bias = w.b_out; a.pre_scale = w.s_out;
-        a.pre_res = h->P; a.pre_out = h->Q;
-      }
-      ldm_handle::Scope sc(h, st, h->pre_out ? "gemm_out_ffn1_ln" : "gemm_ffn1_ln", gemm_flops(M, F, D) + (h->pre_out ? gemm_flops(M, D, D) : 0.0),
-                           (double)M * D * 4 + (double)M * F * 4 + (h->pre_out ? (double)M * D * 12 : 0.0));
+      ldm_handle::Scope sc(h, st, "gemm_ffn1_ln", gemm_flops(M, F, D), (double)M * D * 4 + (double)M * F * 4);
       if (launch_lngemm16x3(a, st)) return h->fail(-4, "row-resident LayerNorm + GEMM: geometry not supported");
     } else {
       {  // LayerNorm 2
@@ -273,10 +261,10 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
         g.C16 = f16 ? h->hid16 : nullptr; g.C16lo = split ? h->hid16lo : nullptr; g.ldc16 = Fp;
         g.M = M; g.N = F; g.K = f16 ? Dp : D; g.lda = f16 ? Dp : D; g.ldw = f16 ? Dp : D; g.precision = prec;
         ldm_handle::Scope sc(h, st, "gemm_ffn1", gemm_flops(M, F, D), (double)M * D * esz + (double)M * F * esz);
-        launch_gemm_mode(g, 2, st);
+        if (int rc = launch_gemm_mode(h, g, 2, st)) return rc;
       }
     }
-    if (!(split && (h->pre_ffn2 || h->ffn_fused))) {  // FFN2 + residual:  P = Q + hid·W2^T + b2   (level 2: the prologue of the next AdaLN + in_proj launch / of the head)
+    if (!(split && h->lngemm)) {  // FFN2 + residual:  P = Q + hid·W2^T + b2   (row-resident: the prologue of the next AdaLN + in_proj launch / of the head)
       GemmArgs g{};
       g.A = f16 ? (const void*)h->hid16 : (const void*)h->hid32;
       g.Alo = h->hid16lo;
@@ -287,7 +275,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
       g.C32 = h->P; g.ldc32 = D;
       g.M = M; g.N = D; g.K = f16 ? Fp : F; g.lda = f16 ? Fp : F; g.ldw = f16 ? Fp : F; g.precision = prec;
       ldm_handle::Scope sc(h, st, "gemm_ffn2", gemm_flops(M, D, F), (double)M * F * esz + (double)M * D * 8);
-      launch_gemm_mode(g, 3, st);
+      if (int rc = launch_gemm_mode(h, g, 3, st)) return rc;
     }
   }
   if (split && h->lngemm) {  // head: LayerNorm + vocabulary projection (no bias) in ONE row-resident launch
@@ -299,7 +287,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
     a.C32 = h->logits; a.ldc32 = h->Cp;
     a.np_main = h->np_ffn;
     a.M = M; a.N = h->Cp; a.D = D; a.S = h->S;   // (columns C .. Cp of the image are zero rows: exact zeros in the padding)
-    const bool hp = h->pre_ffn2 && !h->ffn_fused;
+    const bool hp = !h->ffn_fused;
     if (hp) ffn2_prologue(h, h->layers[h->L - 1], a);
     ldm_handle::Scope sc(h, st, hp ? "gemm_ffn2_head_ln" : "gemm_head_ln", gemm_flops(M, C, D) + (hp ? gemm_flops(M, D, F) : 0.0),
                          (double)M * D * 4 + (double)M * C * 4 + (hp ? (double)M * F * 4 : 0.0));
@@ -325,7 +313,7 @@ int ldm_host::denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int B
     g.C32 = h->logits; g.ldc32 = h->Cp;
     g.M = M; g.N = C; g.K = f16 ? Dp : D; g.lda = f16 ? Dp : D; g.ldw = f16 ? Dp : D; g.precision = prec;
     ldm_handle::Scope sc(h, st, "gemm_head", gemm_flops(M, C, D), (double)M * D * esz + (double)M * C * 4);
-    launch_gemm_mode(g, 4, st);
+    if (int rc = launch_gemm_mode(h, g, 4, st)) return rc;
   }
   return 0;
 }

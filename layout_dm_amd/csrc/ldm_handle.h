@@ -74,11 +74,11 @@ struct LayerW {
   __half *w_in16, *w_in16lo, *w_out16, *w_out16lo, *w1_16, *w1_16lo, *w2_16, *w2_16lo;
   float s_in = 1.f, s_out = 1.f, s1 = 1.f, s2 = 1.f;  // split mode: 2^-k of each tensor's power-of-two pre-scale (GemmArgs.out_scale)
   void *x3_qkv = nullptr, *x3_ffn1 = nullptr;         // split mode: hi | lo tile images of in_proj / linear1 (kernels_lngemm.hip)
-  void *x3_out_slab = nullptr, *x3_ffn2_slab = nullptr;   // ... K-slab images of out_proj / linear2 (its GEMM prologue, lngemm level 2)
+  void* x3_ffn2_slab = nullptr;                      // ... K-slab image of linear2 (the GEMM prologue of the next row-resident launch)
   // r06, fused attention + out_proj (kernels_attnout.hip): in_proj with head-padded output columns (48 tiles, bias [1536]) and
   // out_proj as a k-step image (ldm_pack::pack_x3_kstep_image)
   void *x3_qkv_pad = nullptr, *x3_out_kstep = nullptr;
-  void* ffn16_img = nullptr;   // hybrid: the fused plain-fp16 FFN's chunk image (kernels_ffn16.hip; the fast mode's pack_ffn_image_pipelined)
+  void* ffn16_img = nullptr;   // hybrid: the plain-fp16 FFN's chunk image (kernels_attnout.hip FFN; the fast mode's pack_ffn_image_pipelined)
   float* b_in_pad = nullptr;
 };
 
@@ -148,17 +148,16 @@ struct ldm_handle {
   __half *head_w16 = nullptr, *head_w16lo = nullptr;
   float head_s = 1.f;
   // split mode on the reference's backbone: the three LayerNorm-fed GEMMs (AdaLN + in_proj, norm2 + linear1, head LN + head)
-  // run as ONE row-resident launch each (kernels_lngemm.hip) instead of a LayerNorm launch + gemm16x3_k
+  // run as ONE row-resident launch each (kernels_lngemm.hip) instead of a LayerNorm launch + gemm16x3_k, and linear2 as the GEMM
+  // prologue of the next of them (the next layer's in_proj, or the head) — unless the hybrid mode's FFN is fused (ffn_fused)
   bool lngemm = false;
-  bool lngemm_pre = false;   // level 2: out_proj / linear2 as the GEMM prologue of the row-resident kernel that consumes their sum
-  bool pre_out = false, pre_ffn2 = false;   // ... which of the two (dev: LDM_X3_LNGEMM=3 / 4 = only out_proj / only linear2)
   void* x3_head = nullptr;
   int x3_qkv_tiles = 0, x3_ffn1_tiles = 0, x3_head_tiles = 0;
   // r06: attention and out_proj of the split mode as ONE layout-resident launch (kernels_attnout.hip); q / k / v travel from in_proj
   // to it as head-padded hi / lo fp16 PANELS (qkvp_hi / qkvp_lo: [48][panel_rows][32]); LDM_DEV=1 LDM_X3_ATTNOUT=0: attn16x3_k + gemm16x3_k
   bool attnout = false;
   size_t panel_rows = 0;
-  // r06: the hidden activations (linear1 -> ReLU -> linear2) travel panel-major as well when linear2 is a GEMM prologue (pre_ffn2):
+  // r06: the hidden activations (linear1 -> ReLU -> linear2) travel panel-major as well between linear1 and the linear2 GEMM prologue:
   // full-line stores in linear1's epilogue, 2-KiB-contiguous A loads in the prologue; LDM_DEV=1 LDM_X3_HIDPANEL=0: row-major
   bool hid_panels = false;
   // two-product form of the split mode's WEIGHT GEMMs: activations hi + lo, weights fp16 only (kernels_lngemm.hip / kernels_attnout.hip W2)
@@ -168,11 +167,9 @@ struct ldm_handle {
   // products per k16-step (kernels_lngemm.hip NPM / NPP): of the attention path's GEMMs (in_proj; out_proj: w2p) and of linear1 / linear2 / the head.
   // split 3 / 3, mixed 2 / 2, hybrid 2 / 1 (the FFN and the head in plain fp16: LayerNorm output, hidden activations and weights rounded once)
   int np_w = 3, np_ffn = 3;
-  // hybrid: linear1 + ReLU + linear2 + residual as ONE plain-fp16 launch per block (kernels_ffn16.hip) instead of linear1 -> plain-fp16 panels ->
-  // linear2 as the GEMM prologue of the next launch; LDM_DEV=1 LDM_HYB_FFN=0: the two-launch form
+  // hybrid: linear1 + ReLU + linear2 + residual in plain fp16 behind the attention, in the SAME launch (kernels_attnout.hip FFN): two launches
+  // per block instead of linear1 -> plain-fp16 panels -> linear2 as the GEMM prologue of the next launch; LDM_DEV=1 LDM_HYB_FFN=0: that form
   bool ffn_fused = false;
-  // ... and that FFN behind the attention in the SAME launch (kernels_attnout.hip FFN): two launches per block; LDM_DEV=1 LDM_HYB_ATTNFFN=0: three
-  bool attn_ffn_fused = false;
   bool balanced_chunks = true;   // ldm_loop.cpp run_loop_body: a call's passes share its layouts evenly; LDM_DEV=1 LDM_BALANCED_CHUNKS=0: full chunks + a remainder
   std::vector<void*> owned;    // everything hipMalloc'ed by the handle for its lifetime
   std::vector<void*> derived;  // what ldm_finalize_weights derives from the checkpoint (fp16 / split copies, LDS images, parameter
@@ -216,7 +213,6 @@ struct ldm_handle {
   }
   // fast-mode (fp16 LDS-DMA GEMM + MFMA attention) layout: K padded to 64, heads padded 58 -> 64
   int Dq = 0, HD = 0, Fq = 0, Mpad = 0;
-  int gemm_cfg[5] = {0, 0, 0, 0, 0};  // qkv, attn_out, ffn1, ffn2, head
   struct FastLayer {
     __half *w_in = nullptr, *w_out = nullptr, *w1 = nullptr, *w2 = nullptr;  // head-padded fp16 copies (generic tiled GEMMs)
     void* attn_head_img_ks = nullptr;  // per head: 6 in_proj tiles (k-slot K) + its 2 out-proj slabs (stack kernel)

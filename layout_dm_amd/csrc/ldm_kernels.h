@@ -79,7 +79,7 @@ struct GemmArgs {
   int precision;  // LDM_PREC_*
   float out_scale;  // split mode: 2^-k of the weight tensor's pre-scale 2^k (0 = 1)
 };
-void launch_gemm(const GemmArgs& g, hipStream_t st);
+void launch_gemm(const GemmArgs& g, hipStream_t st);   // exact mode (fp32 operands; kernels_gemm.hip)
 
 // Row-resident (Ada)LayerNorm + fp16 x 3 GEMM (kernels_lngemm.hip): out = epi(LN(x) W^T) with the normalised hi / lo
 // fragments of 128 rows resident in a workgroup's registers and the weights streamed as hi | lo tile images
@@ -102,12 +102,12 @@ struct LnGemmArgs {
   int panel_out;
   size_t panel_stride;      // bytes between panels (>= (M + slack) * 64, a multiple of 16)
   // GEMM prologue (pre_img != nullptr): x = pre_res + pre_bias + pre_scale * (preA · Wpre^T) is computed by the kernel itself instead
-  // of being read — out_proj in front of norm2 + linear1, linear2 in front of the next AdaLN + in_proj / of the head
-  const __half *preA, *preAlo;   // [M, pre_lda] hi / lo rows (attention output / hidden activations), K = 32 * pre_stages columns read
+  // of being read — linear2 in front of the next AdaLN + in_proj / of the head
+  const __half *preA, *preAlo;   // [M, pre_lda] hi / lo rows (hidden activations), K = 32 * pre_stages columns read
   const char* pre_img;           // pre_stages x 64 KiB K-slab image (ldm_pack::pack_x3_slab_image) of Wpre [D, K]
   const float* pre_bias;         // [D]
   const float* pre_res;          // [M, D] fp32 residual rows
-  float* pre_out;                // [M, D] or nullptr: x written back (the residual base of a later GEMM)
+  float* pre_out;                // [M, D] or nullptr: x written back (always nullptr: only the removed out_proj prologue wrote it)
   int pre_lda, pre_stages, pre_astages;   // stages of the image (a multiple of 3, zero slabs at the end) / stages with real K columns
   size_t pre_panel_stride;                // 0: preA / preAlo are row-major; else (r06) panel-major [K / 32][rows][32 halves], bytes between panels
   float pre_scale;
@@ -118,24 +118,14 @@ struct LnGemmArgs {
   int np_main, np_pre;
 };
 int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st);
-// Fused plain-fp16 FFN on rows (kernels_ffn16.hip, the hybrid mode): out = x + b2 + W2 relu(W1 LN(x; gamma, beta) + b1); x / out fp32 [M, D] (may alias),
-// img = ldm_pack::pack_ffn_image_pipelined ((n_chunks + 1) x 64 KiB), D == 464, F == 32 n_chunks <= 2048.  -1: geometry not supported.
-struct FfnRowsArgs {
-  const float* x;
-  float* out;
-  const float *gamma, *beta, *b1, *b2;
-  const char* img;
-  int M, D, F, n_chunks;
-};
-int launch_ffn16_rows(const FfnRowsArgs& a, hipStream_t st);
 void lngemm_phase_read(unsigned long long* out8);   // (LDM_LNGEMM_TM=1: accumulated phase cycles, reset on read)
-// fp16 LDS-DMA pipelined GEMM (kernels_gemm16.hip); cfg selects the tile configuration
-void launch_gemm16(const GemmArgs& g, int cfg, int tag, hipStream_t st);
-int gemm16_block_k(int cfg);
+// fp16 LDS-DMA pipelined GEMM of the fast mode's generic path (kernels_gemm16.hip): K a multiple of kGemm16BK (zero pad columns);
+// tag names the Linear class (0 qkv, 1 attn_out, 2 ffn1, 3 ffn2, 4 head)
+constexpr int kGemm16BK = 64;
+void launch_gemm16(const GemmArgs& g, int tag, hipStream_t st);
 // fp16 x 3 split GEMM on the same pipeline (kernels_gemm16.hip gemm16x3_k): A / Alo / W / Wlo, K % 32 == 0, operand
 // buffers allocated to whole 128-row tiles
 void launch_gemm16x3(const GemmArgs& g, int tag, hipStream_t st);
-void launch_gemm16x3_abl(const GemmArgs& g, int abl, hipStream_t st);  // dev ablations (ldm_dev_bench_gemm_x3)
 // per-layer weights of the stack kernel (all device pointers)
 struct FusedLayerW {
   const void* img;        // ldm_pack::pack_attn_head_image (in_proj K axis in k-slot order)

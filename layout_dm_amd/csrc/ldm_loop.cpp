@@ -58,7 +58,7 @@ static int check_relation(ldm_handle* h, const ldm_relation* rel, const ldm_cond
   // step_all (which may run under stream capture), and only when that form can be reached.
   PostArgs probe{};
   fill_post(h, probe, nullptr, nullptr, 0, 1);
-  const bool three_launch = !loop_fusable(h, rel) && !(relation_step_supported(probe) && knob_int("LDM_REL_FUSED", 1) != 0);
+  const bool three_launch = !loop_fusable(h, rel) && !relation_step_supported(probe);
   for (int l = 0; three_launch && l < h->n_lanes; ++l) {
     if (h->ws[l].rel_logp) continue;
     float* buf = nullptr;
@@ -120,7 +120,7 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
       continue;
     }
     // cond=relation (base.py:243-291): posterior + strong mask -> logit adjustment -> [PAD] disable -> draw
-    if (relation_step_supported(p) && knob_int("LDM_REL_FUSED", 1) != 0) {  // ... in ONE launch (r04)
+    if (relation_step_supported(p)) {  // ... in ONE launch (r04)
       PostArgs q = p;
       q.pad_disable = 1;
       q.tokens_out = tout + (size_t)off * h->S;

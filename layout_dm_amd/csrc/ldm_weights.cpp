@@ -406,9 +406,8 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
         HIP_OK(h, hipMemcpy(w.b_in_pad, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
         if ((rc = make_x3_kstep(h, w.w_out16, w.w_out16lo, D, h->Dp, &w.x3_out_kstep))) return rc;
       }
-      if (h->pre_out && (rc = make_x3_slab(h, w.w_out16, w.w_out16lo, D, h->Dp, h->Dp, &w.x3_out_slab))) return rc;
-      if (h->pre_ffn2 && (rc = make_x3_slab(h, w.w2_16, w.w2_16lo, D, h->Fp, h->Fp, &w.x3_ffn2_slab))) return rc;
-      if (h->ffn_fused) {   // hybrid: the FFN as ONE plain-fp16 launch (kernels_ffn16.hip) on the fast mode's chunk image — unscaled fp16 weights,
+      if (h->lngemm && (rc = make_x3_slab(h, w.w2_16, w.w2_16lo, D, h->Fp, h->Fp, &w.x3_ffn2_slab))) return rc;
+      if (h->ffn_fused) {   // hybrid: the FFN in plain fp16 behind the attention (kernels_attnout.hip) on the fast mode's chunk image — unscaled fp16 weights,
                             // K axes in MFMA k-slot order, stage i = W1 tile i | W2 slab i - 1 (ldm_pack::pack_ffn_image_pipelined)
         auto id = [](int x) { return x; };
         auto kslot = [](int k) { return ldm_pack::kslot(k); };

@@ -705,12 +705,12 @@ def test_logits_bitwise_repeatable(cuda, precision):
             assert torch.equal(again, first), f"{precision} B={B}: repetition {i + 1} differs by {(again - first).abs().max().item():.3e}"
 
 
-@pytest.mark.parametrize("level", ["0", "1", "2", "3"])
+@pytest.mark.parametrize("level", ["0"])
 def test_split_mode_alternative_structures_agree(cuda, monkeypatch, level):
-    """The split mode's other launch structures behind LDM_X3_LNGEMM (dev knob) against the default one and the oracle: 0 = the r04
-    structure (LayerNorm launches + tiled GEMMs), 1 = the row-resident kernels without a GEMM prologue, 2 / 3 = out_proj as a GEMM
-    prologue too / only (default, level 4: linear2 only).  Same numerics class (fp16 x 3, fp32 accumulation): logits within the split mode's tolerance of the oracle and within
-    2e-6 of the default structure; greedy step identical.  Full chunk and ragged batch (the last workgroup's rows are partly masked)."""
+    """The split mode's other launch structure behind LDM_X3_LNGEMM=0 (dev knob) against the default one and the oracle: the r04 structure
+    (LayerNorm launches + tiled GEMMs), which every d_model other than 464 runs.  Same numerics class (fp16 x 3, fp32 accumulation): logits
+    within the split mode's tolerance of the oracle and within 2e-6 of the default structure; greedy step identical.  Full chunk and ragged
+    batch (the last workgroup's rows are partly masked)."""
     from oracle import restatement as R
 
     spec, W = weights("rico25")

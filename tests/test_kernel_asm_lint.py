@@ -133,14 +133,12 @@ def test_step_tail_kernels_use_no_scratch(tmp_path):
                 assert m and int(m.group(1)) == 0, (sym, m and m.group(1))
 
 
-def test_exact_mode_kernels_resources(tmp_path):
+def test_exact_mode_gemm_tile_and_attention_resources(tmp_path):
     """The exact mode's fp32 kernels: no scratch, and the register / LDS footprints their schedules were measured at —
-    the 128 x 128 GEMM tile at <= 102 VGPRs and 32 KB of LDS (5 workgroups per CU), its 64-row and 160-wide variants and the
+    the 128 x 128 GEMM tile at <= 102 VGPRs and 32 KB of LDS (5 workgroups per CU) and the
     fp32 attention (K alone in LDS: 30 KB, <= 170 VGPRs: 3 workgroups per CU).  The GEMMs' operands arrive by LDS-DMA."""
     want = {
         "gemm_f32_tileILi2E": dict(src="kernels_gemm.hip", vgpr=102, lds=32 * 1024),
-        "gemm_f32_tileILi1E": dict(src="kernels_gemm.hip", vgpr=85, lds=24 * 1024),
-        "gemm_f32_128x160": dict(src="kernels_gemm.hip", vgpr=128, lds=36 * 1024),
         "attn32_direct_kILi29E": dict(src="kernels_attn.hip", vgpr=170, lds=0),  # (dynamic LDS: 128 x 59 floats at launch)
     }
     asm_of = {}
@@ -186,7 +184,7 @@ def test_split_mode_kernels_resources(tmp_path):
     assert sum("v_mfma" in i for i in ins) == 96, sym  # 2 x (4 x 4 | 8 x 2) fragment pairs x 3 products
 
 
-def test_lngemm_kernel_no_scratch_and_mfma_hazards(tmp_path):
+def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards(tmp_path):
     """kernels_lngemm.hip (r05): no scratch; no VALU write of an inline-asm MFMA operand inside the verified wait states; and the
     failure class r05 found on hardware — hipcc reading a tile accumulator right behind the asm MFMAs it cannot recognise (two
     builds lost the low-order products that way: logits error 5e-5 instead of 9e-7) — every non-MFMA instruction that READS the
@@ -195,10 +193,21 @@ def test_lngemm_kernel_no_scratch_and_mfma_hazards(tmp_path):
     # the product instantiations (TM = false, ABL = 0: template arguments 3 and 4 mangle as Lb0ELi0; the phase-timer and measurement builds are dev only)
     NAME = re.compile(r"ELb0ELi0ELb([01])ELi([123])ELi([123])EEEvNS_10LnGemmArgsE$")   # ... PRE, NPM, NPP> (products per k16-step: tile loop, GEMM prologue)
     kernels = {k: v for k, v in _kernels(asm).items() if "lngemm16x3_k" in k and NAME.search(k)}
-    # (ADA, OUT) in {(1, 0), (0, 1), (0, 0), (1, 2)} x {plain, with the GEMM prologue} x {three products (split), two (mixed: weights fp16 only)};
-    # OUT = 2 (r06): in_proj writing hi / lo q / k / v panels; + the hybrid mode's three: linear2 in plain fp16 in front of the two-product in_proj,
-    # linear1 in plain fp16 writing plain-fp16 panels (OUT = 3), linear2 + head in plain fp16, the head alone in plain fp16 (behind the fused fp16 FFN)
-    assert len(kernels) == 20, list(_kernels(asm))
+    # the forms ldm_create can reach (kernels_lngemm.hip launch_lngemm16x3 derives them), as <ADA, OUT, PRE, NPM, NPP>; PRE = linear2 of the
+    # previous layer as the GEMM prologue (in_proj from layer 1 on, the head), always but behind the hybrid mode's fused FFN; OUT = 2 (r06): in_proj
+    # writing hi / lo q / k / v panels for the fused attention, OUT = 0 with ADA: in_proj's fp32 rows under LDM_X3_ATTNOUT=0
+    reachable = {
+        # split (three products): in_proj, linear1 (OUT = 1: ReLU, hi / lo), head
+        (1, 2, 0, 3, 3), (1, 2, 1, 3, 3), (1, 0, 0, 3, 3), (1, 0, 1, 3, 3), (0, 1, 0, 3, 3), (0, 0, 1, 3, 3),
+        # mixed (two: weights fp16 only)
+        (1, 2, 0, 2, 2), (1, 2, 1, 2, 2), (0, 1, 0, 2, 2), (0, 0, 1, 2, 2),
+        # hybrid (the FFN and the head in plain fp16): in_proj behind linear2, linear1 writing plain-fp16 panels (OUT = 3), the head behind
+        # linear2 / alone (behind the FFN fused into the attention launch); its layer-0 in_proj is mixed's
+        (1, 2, 1, 2, 1), (0, 3, 0, 1, 1), (0, 0, 1, 1, 1), (0, 0, 0, 1, 1),
+    }
+    FORM = re.compile(r"lngemm16x3_kILb([01])ELi([0-3])ELb0ELi0ELb([01])ELi([123])ELi([123])EEEvNS_10LnGemmArgsE$")
+    assert {tuple(int(x) for x in FORM.search(k).groups()) for k in kernels} == reachable, list(_kernels(asm))
+    assert len(kernels) == 14
     sizes = dict(re.findall(r"\.amdhsa_kernel\s+(\S+)[\s\S]*?\.amdhsa_private_segment_fixed_size\s+(\d+)", asm))
     for name, instr in kernels.items():
         assert int(sizes[name]) == 0 and not [i for i in instr if i.startswith("scratch_")], name
@@ -372,22 +381,3 @@ def _attnout_checks(asm, name, instr, per_head):
             ws += 1
             if ws >= 32:
                 break
-
-
-def test_ffn16_rows_kernel_resources(tmp_path):
-    """kernels_ffn16.hip (r06, the hybrid mode's fused plain-fp16 FFN): the fast mode's chunk stream (ldm_pipes.h FfnStream) as a row kernel — no
-    scratch, all of a CU's LDS budget respected, 59 MFMAs per chunk iteration (29 + 30), and nothing moves between the register files inside the
-    chunk loop (the 15 residual tiles live in AGPRs from the first load to the last store)."""
-    asm = _compile("kernels_ffn16.hip", tmp_path)
-    blocks = re.findall(r"\.amdhsa_kernel\s+(\S*ffn16_rows_k\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S)
-    assert len(blocks) == 1
-    sym, body = blocks[0]
-    get = lambda field: int(re.search(r"\.amdhsa_%s\s+(\d+)" % field, body).group(1))
-    assert get("private_segment_fixed_size") == 0 and get("next_free_vgpr") <= 512
-    ins = _kernels(asm)[sym]
-    assert not [t for t in ins if t.startswith("scratch_")]
-    mf = [i for i, t in enumerate(ins) if "v_mfma_f32_32x32x16" in t]
-    assert len(mf) == 59, len(mf)
-    loop = ins[mf[0]:mf[-1] + 1]
-    assert not [t for t in loop if t.startswith(("v_accvgpr_read", "v_accvgpr_write", "v_accvgpr_mov"))]
-    assert sum("global_load_lds_dwordx4" in t for t in loop) == 16      # one 64-KiB stage per iteration: 16 pieces per wave

@@ -160,7 +160,8 @@ def test_mixed_is_refused_where_its_kernels_do_not_exist(cuda):
 
 
 def test_hybrid_fused_ffn_against_its_two_launch_form_and_the_emulation(cuda, tmp_path):
-    """The hybrid mode's FFN ships as ONE plain-fp16 launch (kernels_ffn16.hip: the fast mode's chunk stream as a row kernel).  Its first form —
+    """The hybrid mode's FFN ships in plain fp16 behind the attention, in the attention launch (kernels_attnout.hip FFN: the fast mode's chunk
+    stream on the attention's accumulator tiles).  Its first form —
     linear1 writing plain-fp16 panels, linear2 as the one-product GEMM prologue of the next launch (kernels_lngemm.hip OUT = 3 / NPP = 1, kept behind
     LDM_DEV=1 LDM_HYB_FFN=0) — rounds the same operands at the same places.  They can NOT be asked to agree digit for digit: a plain-fp16 activation
     format is chaotic at its own error level — a 1e-7 relative perturbation anywhere upstream (another fp32 summation order is enough) flips one
