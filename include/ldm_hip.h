@@ -260,6 +260,30 @@ int ldm_eval_max_iou_pairs(const void* d_bbox1, int box1_f64, const int64_t* d_l
                            int R2, int S, const int64_t* d_groups, int G, int64_t n_pairs, int max_seg, double* d_out,
                            int32_t* d_err, void* stream);
 
+/* ---- relation violation score (compute_violation of the sampling entry point) -------------------------------------------
+ * trainer/helpers/metric.py:62-95 (test.py:230-254): per layout, failures / valid over the edges of its relation graph, with
+ * detect_size_relation / detect_loc_relation (data/util.py:33-69) on the sampled boxes.  Device pointers in and out, no handle,
+ * the current device; box_f64 as above.  The graph is the per-layout CSR edge list of cond["batch_w_canvas"]:
+ * d_edge_off (n_graph+1) int32, d_src / d_dst (n_edge) int32 LOCAL node ids, d_attr (n_edge) int32 relation bitmasks,
+ * d_first_node (n_graph) int64 = the global id of each graph's node 0 as `batch` defines it, d_canvas (n_nodes) uint8 =
+ * (y == 0).  The box row of an edge end is first_node[graph] + local id.  d_out (n_graph) float32 (NaN where no relation is
+ * known, like the reference); d_edge_out (n_edge,3) int32 {size code, loc code, failures} in CSR edge order, or NULL.
+ * *d_err (int32, zeroed by the call): bit 0 = an edge names a row beyond the box rows (the reference raises an IndexError),
+ * bit 1 = malformed graph (offsets, node ids); the scores of such layouts are NaN.  n_graph >= 1; n_edge may be 0.
+ * Returns 0, -1 (bad argument: nothing launched) or -2 (launch failed). */
+/* flattened form: d_bbox (n_rows,4) = bbox_flatten. */
+int ldm_relation_violation(const void* d_bbox, int box_f64, int64_t n_rows, const uint8_t* d_canvas, int64_t n_nodes,
+                           const int32_t* d_edge_off, const int32_t* d_src, const int32_t* d_dst, const int32_t* d_attr,
+                           const int64_t* d_first_node, int n_graph, int n_edge, float* d_out, int32_t* d_edge_out,
+                           int32_t* d_err, void* stream);
+/* dense form: d_bbox (B,S,4) + d_mask (B,S) uint8 as ldm_decode_layouts leaves them; rows are those of bbox_c[mask_c] with the
+ * canvas box (0.5, 0.5, 1, 1) in front of every layout (test.py:232-250).  d_row_start (B+1) int32 is filled with the first
+ * row of every layout (workspace and by-product).  B >= 1, S >= 1. */
+int ldm_relation_violation_dense(const void* d_bbox, int box_f64, const uint8_t* d_mask, int B, int S, int32_t* d_row_start,
+                                 const uint8_t* d_canvas, int64_t n_nodes, const int32_t* d_edge_off, const int32_t* d_src,
+                                 const int32_t* d_dst, const int32_t* d_attr, const int64_t* d_first_node, int n_graph,
+                                 int n_edge, float* d_out, int32_t* d_edge_out, int32_t* d_err, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------- */
 /* average device time (ms) of the most recent ldm_sample_loop, measured with HIP events on the
  * stream it ran on; blocks until that loop has finished. */

@@ -33,6 +33,8 @@ EXPORTS = (
     "ldm_fid_features", "ldm_prdc", "ldm_layout_metrics",
     # average IoU / DocSim / Max-IoU (bound in layout_dm_amd/metrics.py)
     "ldm_eval_average_iou", "ldm_eval_docsim", "ldm_eval_max_iou_pairs",
+    # relation violation score (bound in layout_dm_amd/metrics.py)
+    "ldm_relation_violation", "ldm_relation_violation_dense",
 )
 
 
@@ -129,6 +131,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_eval_average_iou.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     lib.ldm_eval_docsim.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.ldm_eval_max_iou_pairs.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, C.c_int64, i32, vp, vp, vp]
+    graph = [vp, C.c_int64, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]  # canvas, n_nodes, CSR, first_node, counts, out, edge_out, err, stream
+    lib.ldm_relation_violation.argtypes = [vp, i32, C.c_int64] + graph
+    lib.ldm_relation_violation_dense.argtypes = [vp, i32, vp, i32, i32, vp] + graph
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int

@@ -275,3 +275,42 @@ extern "C" int ldm_eval_max_iou_pairs(const void* d_bbox1, int box1_f64, const i
                       (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
+
+// ---- relation violation score (trainer/helpers/metric.py:62-95; kernels_violation.hip).  Every argument is checked before
+// anything is launched.
+static bool violation_graph(ViolationGraph& g, const uint8_t* d_canvas, int64_t n_nodes, const int32_t* d_edge_off,
+                            const int32_t* d_src, const int32_t* d_dst, const int32_t* d_attr, const int64_t* d_first_node,
+                            int n_graph, int n_edge) {
+  if (n_graph < 1 || n_edge < 0 || n_nodes < 0 || !d_edge_off || !d_first_node) return false;
+  if (n_edge > 0 && (!d_src || !d_dst || !d_attr || !d_canvas)) return false;
+  g = ViolationGraph{d_canvas, n_nodes, d_edge_off, d_src, d_dst, d_attr, d_first_node, n_graph, n_edge};
+  return true;
+}
+
+extern "C" int ldm_relation_violation(const void* d_bbox, int box_f64, int64_t n_rows, const uint8_t* d_canvas, int64_t n_nodes,
+                                      const int32_t* d_edge_off, const int32_t* d_src, const int32_t* d_dst,
+                                      const int32_t* d_attr, const int64_t* d_first_node, int n_graph, int n_edge, float* d_out,
+                                      int32_t* d_edge_out, int32_t* d_err, void* stream) {
+  ViolationGraph g;
+  if ((box_f64 != 0 && box_f64 != 1) || n_rows < 0 || (n_rows > 0 && !d_bbox) || !d_out || !d_err) return -1;
+  if (!violation_graph(g, d_canvas, n_nodes, d_edge_off, d_src, d_dst, d_attr, d_first_node, n_graph, n_edge)) return -1;
+  (void)hipGetLastError();
+  if (hipMemsetAsync(d_err, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return -2;
+  launch_relation_violation(d_bbox, box_f64, n_rows, g, d_out, d_edge_out, d_err, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int ldm_relation_violation_dense(const void* d_bbox, int box_f64, const uint8_t* d_mask, int B, int S,
+                                            int32_t* d_row_start, const uint8_t* d_canvas, int64_t n_nodes,
+                                            const int32_t* d_edge_off, const int32_t* d_src, const int32_t* d_dst,
+                                            const int32_t* d_attr, const int64_t* d_first_node, int n_graph, int n_edge,
+                                            float* d_out, int32_t* d_edge_out, int32_t* d_err, void* stream) {
+  ViolationGraph g;
+  if ((box_f64 != 0 && box_f64 != 1) || B < 1 || S < 1 || (int64_t)B * (S + 1) > INT32_MAX) return -1;
+  if (!d_bbox || !d_mask || !d_row_start || !d_out || !d_err) return -1;
+  if (!violation_graph(g, d_canvas, n_nodes, d_edge_off, d_src, d_dst, d_attr, d_first_node, n_graph, n_edge)) return -1;
+  (void)hipGetLastError();
+  if (hipMemsetAsync(d_err, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return -2;
+  launch_relation_violation_dense(d_bbox, box_f64, d_mask, B, S, d_row_start, g, d_out, d_edge_out, d_err, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}

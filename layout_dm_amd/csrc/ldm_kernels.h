@@ -191,6 +191,22 @@ void launch_eval_docsim(const void* bbox1, int box1_f64, const int64_t* label1, 
 void launch_eval_max_iou(const void* bbox1, int box1_f64, const int64_t* label1, int R1, const void* bbox2, int box2_f64, int R2,
                          int S, const int64_t* groups, int G, int64_t n_pairs, int max_seg, double* out, int32_t* err,
                          hipStream_t st);
+// relation violation score (kernels_violation.hip); arguments checked by the C-ABI (ldm_fid_api.cpp)
+struct ViolationGraph {
+  const uint8_t* canvas;       // (n_nodes) 1 where y == 0
+  int64_t n_nodes;
+  const int32_t *edge_off;     // (n_graph+1) CSR offsets into src / dst / attr
+  const int32_t *src, *dst, *attr;  // (n_edge) local node ids, relation bitmask
+  const int64_t* first_node;   // (n_graph) global id of each graph's node 0
+  int n_graph, n_edge;
+};
+// out (n_graph) f32 = failures / valid; edge_out (n_edge,3) i32 {size code, loc code, failures} or nullptr; *err bit 0 = an
+// edge names a row beyond the flattened rows, bit 1 = malformed graph
+void launch_relation_violation(const void* bbox, int box_f64, int64_t n_rows, const ViolationGraph& g, float* out,
+                               int32_t* edge_out, int32_t* err, hipStream_t st);
+// bbox (B,S,4) + mask (B,S) of ldm_decode_layouts, a canvas row in front of every layout; row_start (B+1) i32 is filled
+void launch_relation_violation_dense(const void* bbox, int box_f64, const uint8_t* mask, int B, int S, int32_t* row_start,
+                                     const ViolationGraph& g, float* out, int32_t* edge_out, int32_t* err, hipStream_t st);
 // ids -> {bbox, label, mask} (kernels_decode.hip); centres: [4][n_bin] f64 cluster centres or nullptr (linear bins)
 void launch_decode_layouts(const int32_t* tokens, int B, int E, int A, int n_category, int n_bin,
                            const double* centres, int box_f64, void* bbox, int64_t* label, uint8_t* mask,

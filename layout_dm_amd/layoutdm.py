@@ -179,6 +179,11 @@ class LayoutDM:
         assert inner.num_classes == tokenizer.N_total and inner.max_token_length == tokenizer.max_token_length
         self.model = _ModuleShim(inner, self)
         self._refine_table = None
+        # inside the reference's own test.py main() (class swapped by layout_dm_amd.test_entry) on a GPU: its per-batch
+        # cond=relation score runs on the device too
+        from .reference_hooks import install_violation_dropin
+
+        install_violation_dropin(type(self))
 
     # ---- nn.Module-ish surface ------------------------------------------------------------------
     def to(self, *a, **k):

@@ -15,6 +15,10 @@ The IoU-family metrics of eval.py (metric.py:300-507; eval.py:173-176,211-215) a
 
 over lists of (bbox ndarray, label ndarray) layouts, plus tensor forms `average_iou(bbox, mask)` and
 `docsim(bbox_gt, label_gt, mask_gt, bbox_gen, label_gen, mask_gen)` for what Engine.decode leaves on the device.
+
+The relation violation score the sampling entry point computes after every cond=relation batch (metric.py:62-95;
+test.py:230-254) is `compute_violation(bbox_flatten, data)`, with `relation_violation(bbox, mask, data)` for the dense
+output of Engine.decode and `relation_detect(bbox_flatten, data)` for the per-edge detections.
 """
 from __future__ import annotations
 
@@ -251,3 +255,102 @@ def compute_maximum_iou(layouts_1, layouts_2, disable_parallel: bool = True, n_j
         return 0.0
     scores = np.concatenate(chosen)
     return 0.0 if len(scores) == 0 else scores.mean().item()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Relation violation score (helpers/metric.py:62-95, called at test.py:230-254 after every cond=relation batch).  `data` is
+# cond["batch_w_canvas"]: anything with y, edge_index, edge_attr, batch — a PyG batch, or a dict (relation.graph_to_csr).
+# One wavefront per layout walks the layout's edges (kernels_violation.hip); float32 or float64 boxes.  No CPU fallback.
+
+def _violation_graph(data, dev):
+    """the device arrays ldm_relation_violation* take: (n_graph, n_edge, n_nodes, canvas, off, src, dst, attr, first, order)"""
+    from .relation import graph_to_csr
+
+    get = (lambda k: data[k]) if isinstance(data, dict) else (lambda k: getattr(data, k))
+    batch = torch.as_tensor(get("batch"))
+    if batch.numel() == 0:
+        raise ValueError("compute_violation: empty batch")
+    n_graph = int(batch.max()) + 1
+    off, src, dst, attr, first, order = graph_to_csr(data, n_graph, with_nodes=True)
+    y = torch.as_tensor(get("y")).reshape(-1)
+    if y.numel() != batch.numel():
+        raise ValueError("y / batch length mismatch")
+    canvas = y.eq(0).to(device=dev, dtype=torch.uint8).contiguous()
+    arrays = [t.to(dev).contiguous() for t in (off, src, dst, attr, first)]
+    return (n_graph, int(src.numel()), int(y.numel()), canvas, *arrays, order)
+
+
+def _out_device(data):
+    get = data.get if isinstance(data, dict) else (lambda k: getattr(data, k, None))
+    x = get("x")   # the reference: data.x.device; a graph without boxes answers where its labels live
+    return x.device if isinstance(x, torch.Tensor) else torch.as_tensor(get("y")).device
+
+
+def _violation_launch(dense, dev, b, mask, data, per_edge: bool):
+    n_graph, E, n_nodes, canvas, off, src, dst, attr, first, order = _violation_graph(data, dev)
+    out = torch.empty(n_graph, dtype=torch.float32, device=dev)
+    edge = torch.empty((E, 3), dtype=torch.int32, device=dev) if per_edge else None
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    graph = (canvas.data_ptr(), n_nodes, off.data_ptr(), src.data_ptr(), dst.data_ptr(), attr.data_ptr(), first.data_ptr(),
+             n_graph, E, out.data_ptr(), edge.data_ptr() if per_edge else None, err.data_ptr(), _stream_ptr(dev))
+    lib = load_library()
+    f64 = int(b.dtype == torch.float64)
+    with torch.cuda.device(dev):
+        if dense:
+            B, S = mask.shape
+            if n_graph > B:
+                raise ValueError(f"the graph names {n_graph} layouts, bbox holds {B}")
+            rows = torch.empty(B + 1, dtype=torch.int32, device=dev)
+            name = "ldm_relation_violation_dense"
+            rc = lib.ldm_relation_violation_dense(b.data_ptr(), f64, mask.data_ptr(), B, S, rows.data_ptr(), *graph)
+        else:
+            name = "ldm_relation_violation"
+            rc = lib.ldm_relation_violation(b.data_ptr(), f64, b.shape[0], *graph)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc})")
+    e = int(err.item())   # (synchronises: the temporaries above are done with)
+    if e & 1:
+        raise IndexError("compute_violation: an edge names a node beyond the flattened boxes (the generated masks hold "
+                         "fewer elements than the relation graph expects)")
+    if e:
+        raise ValueError("compute_violation: malformed relation graph")
+    return out, edge, order
+
+
+def _flat_boxes(bbox_flatten: torch.Tensor, dev):
+    if bbox_flatten.dim() != 2 or bbox_flatten.shape[-1] != 4:
+        raise ValueError(f"bbox_flatten must be (rows,4); got {tuple(bbox_flatten.shape)}")
+    dt = torch.float64 if bbox_flatten.dtype == torch.float64 else torch.float32
+    return bbox_flatten.to(device=dev, dtype=dt).contiguous()
+
+
+def compute_violation(bbox_flatten: torch.Tensor, data) -> torch.Tensor:
+    """helpers/metric.py:62-95: float32 (batch.max() + 1,) failures / valid per layout (NaN where no relation is known), on
+    data.x.device (the graph's device).  bbox_flatten (rows,4) = bbox_c[mask_c] of test.py:232-250, indexed by the graph's global node ids."""
+    dev = bbox_flatten.device if bbox_flatten.is_cuda else _device()
+    out, _, _ = _violation_launch(False, dev, _flat_boxes(bbox_flatten, dev), None, data, False)
+    return out.to(_out_device(data))
+
+
+def relation_violation(bbox: torch.Tensor, mask: torch.Tensor, data) -> torch.Tensor:
+    """compute_violation on the dense output of Engine.decode / LayoutDM.sample — bbox (B,S,4), mask (B,S) — without
+    building bbox_c[mask_c]: the canvas row in front of every layout and the flattening by mask (test.py:232-250) happen in
+    the kernel.  Inputs and the float32 (batch.max() + 1,) result stay on the device."""
+    dev = bbox.device if bbox.is_cuda else _device()
+    if bbox.dim() != 3 or bbox.shape[-1] != 4 or tuple(mask.shape) != tuple(bbox.shape[:2]) or 0 in mask.shape:
+        raise ValueError(f"bbox must be (B,S,4) and mask (B,S), B, S >= 1; got {tuple(bbox.shape)}, {tuple(mask.shape)}")
+    dt = torch.float64 if bbox.dtype == torch.float64 else torch.float32
+    out, _, _ = _violation_launch(True, dev, bbox.to(device=dev, dtype=dt).contiguous(),
+                                  mask.to(device=dev, dtype=torch.uint8).contiguous(), data, False)
+    return out
+
+
+def relation_detect(bbox_flatten: torch.Tensor, data):
+    """Per edge, in edge_index's order: (size_code, loc_code, failure) int32 tensors on the device — what
+    detect_size_relation / detect_loc_relation (data/util.py:33-69, RelSize 1..3, RelLoc 5..9) say about the boxes, and how
+    many of the relations edge_attr knows they break (0..2)."""
+    dev = bbox_flatten.device if bbox_flatten.is_cuda else _device()
+    _, edge, order = _violation_launch(False, dev, _flat_boxes(bbox_flatten, dev), None, data, True)
+    back = torch.empty_like(edge)
+    back[order.to(dev)] = edge
+    return back[:, 0].contiguous(), back[:, 1].contiguous(), back[:, 2].contiguous()

@@ -23,11 +23,13 @@ import torch
 from .diffusion import HipMaskAndReplaceDiffusion, _cfg_get, batch_cuts, timestep_schedule
 
 
-def graph_to_csr(graph, n_graph: int):
+def graph_to_csr(graph, n_graph: int, with_nodes: bool = False):
     """cond["batch_w_canvas"] (torch_geometric DataBatch fields: batch (nodes,), edge_index (2,E) GLOBAL node ids,
     edge_attr (E,); helpers/task.py:112-114, data/util.py:128-177) -> per-layout CSR with LOCAL node ids, the form
     ldm_relation_update takes: (offsets int32 (n_graph+1,), src int32 (E,), dst int32 (E,), attr int32 (E,)), edges
-    of a layout kept in their original order."""
+    of a layout kept in their original order.  with_nodes=True appends what addresses rows by GLOBAL node id (the violation
+    score, metrics.py): first int64 (n_graph,), each layout's first node id, and order int64 (E,), the original position of
+    every CSR edge."""
     get = (lambda k: graph[k]) if isinstance(graph, dict) else (lambda k: getattr(graph, k))
     batch = torch.as_tensor(get("batch")).long().cpu()
     ei = torch.as_tensor(get("edge_index")).long().cpu().reshape(2, -1)
@@ -44,7 +46,8 @@ def graph_to_csr(graph, n_graph: int):
     order = torch.argsort(eg, stable=True)
     eg, src, dst, ea = eg[order], ei[0][order], ei[1][order], ea[order]
     off = torch.cat([eg.new_zeros(1), torch.bincount(eg, minlength=n_graph).cumsum(0)])
-    return off.int(), (src - first[eg]).int(), (dst - first[eg]).int(), ea.int()
+    csr = off.int(), (src - first[eg]).int(), (dst - first[eg]).int(), ea.int()
+    return csr + (first, order) if with_nodes else csr
 
 
 def relation_geometry(tokenizer):

@@ -3,6 +3,7 @@ workload; prints ONE JSON line.
 
     python tools/eval_metrics_bench.py [--layouts 3000] [--iters 5]          # on the MI355X
     python tools/eval_metrics_bench.py --reference-cpu 300                    # the reference's CPU cost per pair (needs it)
+    python tools/eval_metrics_bench.py --violation [--iters 20]               # the relation violation score instead
 
 Workload: two sets of `--layouts` layouts whose label multisets come from a handful of keys (a 6-element key, a 12-element
 one and a 25-element one with segments of 1 - 10 equal labels), so that Max-IoU groups hold hundreds of layouts and the pair
@@ -13,6 +14,12 @@ device_ms: HIP events around the C-ABI launch on inputs already in HBM (warmed u
 end_to_end_ms: the drop-in from the Python lists (packing, copies, the launch, and for Max-IoU scipy's per-group
 assignment on the host).  --reference-cpu N times the reference's own per-pair / per-layout functions on N problems of the
 same workload on the CPU (single process, as eval.py runs them: DISABLED = True).
+
+--violation: compute_violation (kernels_violation.hip) on the 512-layout relation batch of
+tests/golden/relation_violation/reference.npz (7 267 nodes, 11 643 edges) and on 8 copies of it (4 096 layouts): device_ms
+of the flattened and the dense entry point, end_to_end_ms of metrics.compute_violation as test.py:251 calls it (boxes on
+the GPU, the graph on the host; includes the host-side CSR build, whose share is reported as csr_ms), and — where the
+reference is importable — the reference's own function called the same way and on CPU tensors.
 """
 from __future__ import annotations
 
@@ -144,6 +151,90 @@ def gpu(args):
     print(json.dumps(res))
 
 
+def violation_workload(copies: int):
+    fx = np.load(os.path.join(ROOT, "tests", "golden", "relation_violation", "reference.npz"))
+    box, y, ei, ea, batch = (fx["big_box"], fx["big_y"].astype(np.int64), fx["big_edge_index"].astype(np.int64),
+                             fx["big_edge_attr"].astype(np.int64), fx["big_batch"].astype(np.int64))
+    n, B = len(y), int(batch.max()) + 1
+    return (np.tile(box, (copies, 1)), np.tile(y, copies), np.concatenate([ei + c * n for c in range(copies)], 1),
+            np.tile(ea, copies), np.concatenate([batch + c * B for c in range(copies)]))
+
+
+def violation(args):
+    import torch
+
+    from layout_dm_amd import metrics as M
+    from layout_dm_amd.binding import _stream_ptr, load_library
+    from layout_dm_amd.relation import graph_to_csr
+    from oracle import ref_harness as rh
+
+    lib, dev = load_library(), torch.device("cuda", 0)
+    st = _stream_ptr(dev)
+    ref = None
+    if rh.reference_importable():
+        rh.install_stubs()
+        from trainer.helpers import metric as ref
+    res = {"device": torch.cuda.get_device_name(0), "reference_importable": ref is not None, "iters": args.iters}
+
+    def wall_ms(fn, reps):
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(ts))
+
+    for copies in (1, 8):
+        box, y, ei, ea, batch = violation_workload(copies)
+        data = rh.GraphBatch(*(torch.from_numpy(v) for v in (y, ei, ea, batch)))
+        data.x = torch.from_numpy(box)
+        bx = data.x.to(dev)
+        n_graph, E, n_nodes, canvas, off, src, dst, attr, first, _ = M._violation_graph(data, dev)
+        out = torch.empty(n_graph, dtype=torch.float32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        g = (canvas.data_ptr(), n_nodes, off.data_ptr(), src.data_ptr(), dst.data_ptr(), attr.data_ptr(), first.data_ptr(), n_graph,
+             E, out.data_ptr(), None, err.data_ptr(), st)
+        # the dense layout of the same rows: elements first in their rows, the canvas row left to the kernel
+        n = np.bincount(batch)
+        S = int(n.max()) - 1
+        mask = np.arange(S)[None, :] < (n - 1)[:, None]
+        dense = np.zeros((n_graph, S, 4), np.float32)
+        assert int((y == 0).sum()) == n_graph      # one canvas node per layout, its first
+        dense[mask] = box[y != 0]
+        tb, tm = torch.from_numpy(dense).to(dev), torch.from_numpy(mask.astype(np.uint8)).to(dev)
+        rows = torch.empty(n_graph + 1, dtype=torch.int32, device=dev)
+
+        def flat():
+            assert lib.ldm_relation_violation(bx.data_ptr(), 0, len(bx), *g) == 0
+
+        def dens():
+            assert lib.ldm_relation_violation_dense(tb.data_ptr(), 0, tm.data_ptr(), n_graph, S, rows.data_ptr(), *g) == 0
+
+        leg = {"layouts": n_graph, "nodes": n_nodes, "edges": E}
+        for name, fn in (("flat", flat), ("dense", dens)):
+            for _ in range(args.warmup):
+                fn()
+            leg[f"{name}_device_ms"] = _median_ms(fn, args.iters)
+            leg[f"{name}_err"] = int(err.item())
+            leg[f"{name}_nan"] = int(out.isnan().sum())
+        for _ in range(args.warmup):
+            M.compute_violation(bx, data)
+        leg["end_to_end_ms"] = wall_ms(lambda: M.compute_violation(bx, data), args.iters)
+        leg["csr_ms"] = wall_ms(lambda: graph_to_csr(data, n_graph, with_nodes=True), args.iters)
+        leg["dense_end_to_end_ms"] = wall_ms(lambda: M.relation_violation(tb, tm, data), args.iters)
+        mine = M.compute_violation(bx, data)
+        if ref is not None:
+            leg["reference_gpu_tensors_ms"] = wall_ms(lambda: ref.compute_violation(bx, data), 1)
+            leg["reference_cpu_tensors_ms"] = wall_ms(lambda: ref.compute_violation(data.x, data), 1)
+            want = ref.compute_violation(data.x, data)
+            leg["equal_to_reference"] = bool(torch.equal(mine.isnan(), want.isnan())
+                                             and torch.equal(mine[~mine.isnan()], want[~want.isnan()]))
+        res[f"x{copies}"] = leg
+    print(json.dumps(res))
+
+
 def reference_cpu(args):
     """the reference's own functions on N problems of the same workload (on the CPU, one process)"""
     import importlib
@@ -197,8 +288,11 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reference-cpu", type=int, default=0, help="time the reference's CPU functions on N problems instead")
+    ap.add_argument("--violation", action="store_true", help="time the relation violation score instead")
     args = ap.parse_args()
-    if args.reference_cpu:
+    if args.violation:
+        violation(args)
+    elif args.reference_cpu:
         reference_cpu(args)
     else:
         gpu(args)
