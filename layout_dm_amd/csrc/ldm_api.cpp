@@ -130,24 +130,10 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
   auto A = [&](auto** p, size_t n) {
     if (rc == 0) rc = h->dalloc(p, n);
   };
-  for (int lane = 0; lane < h->n_lanes; ++lane) {
-  // P / Q carry padding rows up to the next multiple of 256: the row-stationary kernels write whole 128-row
-  // blocks (rows >= M land in the padding instead of being exec-masked)
-  const size_t Mrows = (size_t)round_up((int)Mc, 256);
-  A(&h->P, Mrows * h->D);
-  A(&h->Q, Mrows * h->D);
-  A(&h->logits, Mc * h->Cp);
-  if (cfg->precision == LDM_PREC_EXACT_F32) {
-    A(&h->qkv32, Mc * 3 * h->D);
-    A(&h->att32, Mc * h->D);
-    A(&h->h32, Mc * h->D);
-    A(&h->hid32, Mc * h->F);
-  } else if (cfg->precision == LDM_PREC_FAST_F16) {
+  if (cfg->precision == LDM_PREC_FAST_F16) {
     h->Dq = round_up(h->D, 64);
     h->HD = h->H * 64;
     h->Fq = round_up(h->F, 64);
-    h->Mpad = round_up((int)Mc, 256);
-    const size_t Mp = h->Mpad;
     if (const char* fa = knob_env("LDM_FUSED_ATTN")) h->fused_attn = atoi(fa) == 0 ? 0 : 6;
     if (const char* sp = knob_env("LDM_STACK_LOOP")) h->stack_loop = atoi(sp);
     h->rel_loop = knob_int("LDM_REL_LOOP", 1);
@@ -156,41 +142,53 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     if (h->S > 128 || h->S <= 96 || h->dh > 64 || h->D != 464 || h->Dq != 512 || h->HD != 512 || h->H != 8 ||
         h->F % 32 || h->F > 2048 || h->L > 8 || h->Cp % 32)
       h->fused_attn = 0;
-    A(&h->att16, Mp * h->HD);
-    A(&h->qkv16, Mp * 3 * h->HD);
-    A(&h->stats_a, Mp);
-    A(&h->stats_b, Mp);
-    if (h->fused_attn == 0) {  // LayerNorm outputs and the FFN hidden activation only exist on the generic path
-      A(&h->a16, Mp * h->Dq);
-      A(&h->h16, Mp * h->Dq);
-      A(&h->hid16, Mp * h->Fq);
-    }
-  } else {
-    // (whole 128-row tiles: the LDS-DMA split GEMM loads its operands without bounds checks)
-    const size_t Mt = (size_t)round_up((int)Mc, 256);
-    A(&h->a16, Mt * h->Dp);
-    A(&h->att16, Mt * h->Dp);
-    A(&h->h16, Mt * h->Dp);
-    A(&h->hid16, (Mt + 64) * h->Fp);     // (+ 64 rows: the panel-major form of the hidden activations, rows rounded up to 64)
-    {
-      A(&h->qkv32, Mc * 3 * h->D);
-      A(&h->a16lo, Mt * h->Dp);
-      A(&h->att16lo, Mt * h->Dp);
-      A(&h->h16lo, Mt * h->Dp);
-      A(&h->hid16lo, (Mt + 64) * h->Fp);
-    }
-    // panel rows: the fused attention kernel reads 128 keys / query rows from a layout's first row whatever S is — the last layout of
-    // a chunk reaches 128 - S rows past the chunk's last row (r06 fix: the slack was the reference's 3 rows + 5; at S = 50 the last
-    // panel was over-read by 8 rows, a memory fault whenever the allocation ended on a page boundary)
-    if (cfg->precision == LDM_PREC_SPLIT_F16) h->panel_rows = (size_t)round_up((int)Mc + std::max(8, 128 - h->S), 64);
-    if (cfg->precision == LDM_PREC_SPLIT_F16 && attnout16x3_supported(h->S, h->H, h->dh, h->D)) {
-      // q / k / v panels of the fused attention + out_proj kernel: 3 x 8 heads x 2 panels of 32 halfs, hi and lo; a layout's last
-      // key tile reads up to 3 rows past the chunk's last row (slack, zero)
-      A(&h->qkvp_hi, (size_t)48 * h->panel_rows * 32);
-      A(&h->qkvp_lo, (size_t)48 * h->panel_rows * 32);
-    }
   }
-  h->save_ws(lane);
+  for (int lane = 0; lane < h->n_lanes; ++lane) {   // one workspace per lane (ldm_handle.h Workspace)
+    Workspace& ws = h->ws[lane];
+    // P / Q carry padding rows up to the next multiple of 256: the row-stationary kernels write whole 128-row
+    // blocks (rows >= M land in the padding instead of being exec-masked)
+    const size_t Mrows = (size_t)round_up((int)Mc, 256);
+    A(&ws.P, Mrows * h->D);
+    A(&ws.Q, Mrows * h->D);
+    A(&ws.logits, Mc * h->Cp);
+    if (cfg->precision == LDM_PREC_EXACT_F32) {
+      A(&ws.qkv32, Mc * 3 * h->D);
+      A(&ws.att32, Mc * h->D);
+      A(&ws.h32, Mc * h->D);
+      A(&ws.hid32, Mc * h->F);
+    } else if (cfg->precision == LDM_PREC_FAST_F16) {
+      const size_t Mp = (size_t)round_up((int)Mc, 256);
+      A(&ws.att16, Mp * h->HD);
+      A(&ws.qkv16, Mp * 3 * h->HD);
+      A(&ws.stats_a, Mp);
+      if (h->fused_attn == 0) {  // LayerNorm outputs and the FFN hidden activation only exist on the generic path
+        A(&ws.a16, Mp * h->Dq);
+        A(&ws.h16, Mp * h->Dq);
+        A(&ws.hid16, Mp * h->Fq);
+      }
+    } else {
+      // (whole 128-row tiles: the LDS-DMA split GEMM loads its operands without bounds checks)
+      const size_t Mt = (size_t)round_up((int)Mc, 256);
+      A(&ws.a16, Mt * h->Dp);
+      A(&ws.att16, Mt * h->Dp);
+      A(&ws.h16, Mt * h->Dp);
+      A(&ws.hid16, (Mt + 64) * h->Fp);     // (+ 64 rows: the panel-major form of the hidden activations, rows rounded up to 64)
+      A(&ws.qkv32, Mc * 3 * h->D);
+      A(&ws.a16lo, Mt * h->Dp);
+      A(&ws.att16lo, Mt * h->Dp);
+      A(&ws.h16lo, Mt * h->Dp);
+      A(&ws.hid16lo, (Mt + 64) * h->Fp);
+      // panel rows: the fused attention kernel reads 128 keys / query rows from a layout's first row whatever S is — the last layout of
+      // a chunk reaches 128 - S rows past the chunk's last row (r06 fix: the slack was the reference's 3 rows + 5; at S = 50 the last
+      // panel was over-read by 8 rows, a memory fault whenever the allocation ended on a page boundary)
+      h->panel_rows = (size_t)round_up((int)Mc + std::max(8, 128 - h->S), 64);
+      if (attnout16x3_supported(h->S, h->H, h->dh, h->D)) {
+        // q / k / v panels of the fused attention + out_proj kernel: 3 x 8 heads x 2 panels of 32 halfs, hi and lo; a layout's last
+        // key tile reads up to 3 rows past the chunk's last row (slack, zero)
+        A(&ws.qkvp_hi, (size_t)48 * h->panel_rows * 32);
+        A(&ws.qkvp_lo, (size_t)48 * h->panel_rows * 32);
+      }
+    }
   }
   if (cfg->precision == LDM_PREC_SPLIT_F16) {
     // the LayerNorm-fed GEMMs as row-resident launches (kernels_lngemm.hip): d_model 464 (29 k16-steps, K padded to 512),
@@ -210,7 +208,7 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     h->hid_panels = h->lngemm && h->panel_rows <= (size_t)round_up((int)Mc, 256) + 64 && knob_int("LDM_X3_HIDPANEL", 1) != 0;
     // r06: attention + out_proj as one layout-resident launch behind an in_proj that writes hi / lo panels (kernels_attnout.hip);
     // LDM_DEV=1 LDM_X3_ATTNOUT=0: attn16x3_k + the out_proj launch of gemm16x3_k (the r05 structure)
-    h->attnout = h->lngemm && h->qkvp_hi && h->panel_rows * 64 * 2 < (1ull << 32) && knob_int("LDM_X3_ATTNOUT", 1) != 0;
+    h->attnout = h->lngemm && h->ws[0].qkvp_hi && h->panel_rows * 64 * 2 < (1ull << 32) && knob_int("LDM_X3_ATTNOUT", 1) != 0;
     h->mixed = mixed;
     h->w2p = h->lngemm && h->attnout && mixed && (mixed == 1 || h->hid_panels);
     if (h->w2p) {
@@ -223,8 +221,6 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
       rc = -1;
     }
   }
-  h->cur_lane = h->n_lanes - 1;
-  h->activate(0);
   A(&h->tok_a, (size_t)cfg->max_batch * h->S);
   A(&h->tok_b, (size_t)cfg->max_batch * h->S);
   A(&h->st_cond_seq, (size_t)cfg->max_batch * h->S);
@@ -284,10 +280,11 @@ extern "C" int ldm_denoise_logits(ldm_handle* h, const int32_t* d_tokens, int t,
   if (t < 0 || t >= h->T) return h->fail(-1, "timestep out of range");
   ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
+  Workspace& ws = h->ws[0];
   for (int off = 0; off < B; off += h->chunk) {
     const int Bc = std::min(h->chunk, B - off);
-    if ((rc = denoise_chunk(h, d_tokens + (size_t)off * h->S, t, Bc, st))) return rc;
-    HIP_OK(h, hipMemcpy2DAsync(d_logits + (size_t)off * h->S * h->C, (size_t)h->C * 4, h->logits, (size_t)h->Cp * 4,
+    if ((rc = denoise_chunk(h, ws, d_tokens + (size_t)off * h->S, t, Bc, st))) return rc;
+    HIP_OK(h, hipMemcpy2DAsync(d_logits + (size_t)off * h->S * h->C, (size_t)h->C * 4, ws.logits, (size_t)h->Cp * 4,
                                (size_t)h->C * 4, (size_t)Bc * h->S, hipMemcpyDeviceToDevice, st));
   }
   HIP_OK(h, hipGetLastError());

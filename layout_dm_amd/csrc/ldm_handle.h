@@ -54,11 +54,6 @@ struct DeviceGuard {
   if (_dev_guard.err != hipSuccess) return (h)->fail(-2, "hipSetDevice(%d) failed: %s", (h)->device,    \
                                                      hipGetErrorString(_dev_guard.err))
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 struct Raw {  // a checkpoint tensor as uploaded (fp32, device)
   float* d = nullptr;
   std::vector<int64_t> shape;
@@ -132,6 +127,19 @@ struct GraphEntry {
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 
+// The activations of ONE chunk of layouts on their way through the denoiser.  A mode allocates the members its launches use
+// (ldm_create) and leaves the others nullptr.
+struct Workspace {
+  float *P = nullptr, *Q = nullptr;   // residual stream, ping-pong [rows, D]
+  float* logits = nullptr;            // [chunk * S, Cp]
+  float *qkv32 = nullptr, *att32 = nullptr, *h32 = nullptr, *hid32 = nullptr;   // exact (qkv32: split as well)
+  __half *a16 = nullptr, *att16 = nullptr, *h16 = nullptr, *hid16 = nullptr, *qkv16 = nullptr;       // fast / split: fp16 (hi) operands
+  __half *a16lo = nullptr, *att16lo = nullptr, *h16lo = nullptr, *hid16lo = nullptr;                 // split: their lo halves
+  __half *qkvp_hi = nullptr, *qkvp_lo = nullptr;   // split, row-resident: q / k / v as head-padded panels [48][panel_rows][32]
+  float2* stats_a = nullptr;          // fast, stack kernel: per-row (mean, rstd) of the raw embedding rows in P
+  float* rel_logp = nullptr;          // cond=relation, three-launch step: adjusted log-probabilities (chunk, C, S); allocated by check_relation
+};
+
 struct ldm_handle {
   ldm_config cfg{};
   int device = 0;
@@ -176,43 +184,19 @@ struct ldm_handle {
                                // tables): freed and rebuilt when the weights are finalized again (a reload used to leak them)
   bool to_derived = false;     // dalloc's destination while ldm_finalize_weights runs
   int n_cu = 256;              // compute units of the device: the batch quantum of the one-launch loop (one workgroup per layout)
-  // workspace of ONE chunk.  These are the pointers the launch sequences use; with several lanes (below) they are
-  // switched to the lane's own buffers by activate() before its launches are recorded / issued.
-  float *P = nullptr, *Q = nullptr, *qkv32 = nullptr, *att32 = nullptr, *h32 = nullptr, *hid32 = nullptr,
-        *logits = nullptr;
-  __half *a16 = nullptr, *a16lo = nullptr, *qkv16 = nullptr, *att16 = nullptr, *att16lo = nullptr, *h16 = nullptr,
-         *h16lo = nullptr, *hid16 = nullptr, *hid16lo = nullptr, *qkvp_hi = nullptr, *qkvp_lo = nullptr;
-  // Lanes: chunks c, c + n_lanes, ... form lane (c % n_lanes); every lane has its own workspace, stream and
-  // captured graph, and the lanes run CONCURRENTLY, lane l starting l * lane_offset_us late.  Why: the fused
-  // kernels alternate HBM-bound phases (row loads / stores, ~30 % of a block) with MFMA-bound phases, and with one
-  // kernel on the whole chip every CU hits the memory phase at the same moment (all-CU burst ~4 TB/s, then HBM
-  // idles).  Two half-chip kernels out of phase halve each burst (profiles/r02_call2_phase_vs_blocks.txt).
-  struct Workspace {
-    float *P, *Q, *qkv32, *att32, *h32, *hid32, *logits, *rel_logp;
-    __half *a16, *a16lo, *qkv16, *att16, *att16lo, *h16, *h16lo, *hid16, *hid16lo, *qkvp_hi, *qkvp_lo;
-    float2 *stats_a, *stats_b;
-  };
+  // Lanes: chunks c, c + n_lanes, ... form lane (c % n_lanes); every lane has its own workspace (ws[lane]: what its launches
+  // and its captured graph are given), stream and captured graph, and the lanes run CONCURRENTLY, lane l starting
+  // l * lane_offset_us late.  Why: the fused kernels alternate HBM-bound phases (row loads / stores, ~30 % of a block) with
+  // MFMA-bound phases, and with one kernel on the whole chip every CU hits the memory phase at the same moment (all-CU burst
+  // ~4 TB/s, then HBM idles).  Two half-chip kernels out of phase halve each burst (profiles/r02_call2_phase_vs_blocks.txt).
+  // The parity hooks and the loop without graphs run every chunk through ws[0].
   std::vector<Workspace> ws;
   std::vector<hipStream_t> lane_stream;
   std::vector<hipEvent_t> lane_done;
   hipEvent_t fork_ev = nullptr;
-  int n_lanes = 1, lane_offset_us = 0, cur_lane = -1;
-  void save_ws(int l) {
-    ws[l] = Workspace{P, Q, qkv32, att32, h32, hid32, logits, rel_logp, a16, a16lo, qkv16, att16, att16lo,
-                      h16, h16lo, hid16, hid16lo, qkvp_hi, qkvp_lo, stats_a, stats_b};
-  }
-  void activate(int l) {
-    if (l == cur_lane) return;
-    if (cur_lane >= 0) ws[cur_lane].rel_logp = rel_logp;  // (allocated lazily)
-    const Workspace& w = ws[l];
-    P = w.P; Q = w.Q; qkv32 = w.qkv32; att32 = w.att32; h32 = w.h32; hid32 = w.hid32; logits = w.logits;
-    rel_logp = w.rel_logp; a16 = w.a16; a16lo = w.a16lo; qkv16 = w.qkv16; att16 = w.att16; att16lo = w.att16lo;
-    h16 = w.h16; h16lo = w.h16lo; hid16 = w.hid16; hid16lo = w.hid16lo; qkvp_hi = w.qkvp_hi; qkvp_lo = w.qkvp_lo;
-    stats_a = w.stats_a; stats_b = w.stats_b;
-    cur_lane = l;
-  }
+  int n_lanes = 1, lane_offset_us = 0;
   // fast-mode (fp16 LDS-DMA GEMM + MFMA attention) layout: K padded to 64, heads padded 58 -> 64
-  int Dq = 0, HD = 0, Fq = 0, Mpad = 0;
+  int Dq = 0, HD = 0, Fq = 0;
   struct FastLayer {
     __half *w_in = nullptr, *w_out = nullptr, *w1 = nullptr, *w2 = nullptr;  // head-padded fp16 copies (generic tiled GEMMs)
     void* attn_head_img_ks = nullptr;  // per head: 6 in_proj tiles (k-slot K) + its 2 out-proj slabs (stack kernel)
@@ -223,7 +207,6 @@ struct ldm_handle {
   std::vector<FastLayer> fast;
   __half* fast_head = nullptr;
   void* head_img_ks = nullptr;  // vocabulary head as 32-class tile images, K axis in k-slot order (stack kernel)
-  float2 *stats_a = nullptr, *stats_b = nullptr;  // deferred normalisation: per-row (mean, rstd) of P / Q
   int fused_attn = 6;  // 6: the layout-resident stack kernel (kernels_stack.hip: all layers + vocabulary head per launch, rows
                        //    in the out-projection accumulators; the reference's backbone on both of its datasets);
                        // 0: generic tiled kernels (LayerNorm -> gemm16 -> attention16 -> ...) for every other accepted
@@ -243,8 +226,7 @@ struct ldm_handle {
   uint8_t* st_strong = nullptr;
   float* st_weak = nullptr;
   int32_t* st_inter = nullptr;  // (n_step, max_batch, S) intermediates of a graph-captured loop
-  // cond=relation: the adjusted log-probabilities of one chunk + staging of the caller's graph (fixed addresses)
-  float* rel_logp = nullptr;            // (chunk, C, S)
+  // cond=relation: staging of the caller's graph (fixed addresses)
   int32_t* st_rel_off = nullptr;        // (max_batch + 1)
   int32_t* st_rel_edges = nullptr;      // 3 x st_rel_cap : src | dst | attr
   size_t st_rel_cap = 0;
@@ -336,7 +318,7 @@ struct ldm_handle {
 namespace ldm_host {
 std::string& create_error();   // last ldm_create error of this thread (ldm_last_error(NULL))
 double gemm_flops(int M, int N, int K);
-int denoise_chunk(ldm_handle* h, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false);
+int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false);
 void fill_post(ldm_handle* h, ldm::PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off, int Bc);
 int check_ready(ldm_handle* h, int B);
 int check_sampler(ldm_handle* h, const ldm_sampler* s);

@@ -30,7 +30,6 @@ void ldm_host::fill_post(ldm_handle* h, PostArgs& p, const ldm_cond* cond, const
 
 int ldm_host::check_ready(ldm_handle* h, int B) {
   if (!h) return -1;
-  h->activate(0);
   if (!h->finalized) return h->fail(-5, "weights not finalized: call ldm_finalize_weights first");
   if (B < 1 || B > h->cfg.max_batch) return h->fail(-1, "batch %d outside [1, max_batch=%d]", B, h->cfg.max_batch);
   return 0;
@@ -65,7 +64,6 @@ static int check_relation(ldm_handle* h, const ldm_relation* rel, const ldm_cond
     int rc = h->dalloc(&buf, (size_t)h->chunk * h->C * h->S, false);
     if (rc) return rc;
     h->ws[l].rel_logp = buf;
-    if (l == h->cur_lane) h->rel_logp = buf;
   }
   return 0;
 }
@@ -80,10 +78,10 @@ void ldm_host::fill_rel(ldm_handle* h, RelArgs& a, const ldm_relation* rel, size
   a.n_category = h->cfg.n_category; a.n_bin = h->cfg.n_bin; a.pad_id = h->vocab.pad_id;
 }
 
-// one fused reverse step over the whole batch, chunk by chunk.  `cond` / `rel` describe layouts 0..B of THIS call
-// (the loop body hands over pointers already advanced to its chunk); rel_layout_off = position of row 0 inside the
-// relation graph's CSR offsets.
-static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_model, int t_post, const ldm_cond* cond,
+// one fused reverse step over the whole batch, chunk by chunk through the workspace `ws`.  `cond` / `rel` describe layouts
+// 0..B of THIS call (the loop body hands over pointers already advanced to its chunk); rel_layout_off = position of row 0
+// inside the relation graph's CSR offsets.
+static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* tout, int t_model, int t_post, const ldm_cond* cond,
                     const ldm_relation* rel, size_t rel_layout_off, const ldm_sampler* s, int step, int B,
                     size_t rng_layout_off, hipStream_t st, bool skip_embed = false, bool embed_next = false,
                     int tie_row = -1) {
@@ -91,11 +89,11 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
     return h->fail(-1, "timestep out of range [0,%d)", h->T);  // constrained.py:139
   for (int off = 0; off < B; off += h->chunk) {
     const int Bc = std::min(h->chunk, B - off);
-    int rc = denoise_chunk(h, tin + (size_t)off * h->S, t_model, Bc, st, skip_embed);
+    int rc = denoise_chunk(h, ws, tin + (size_t)off * h->S, t_model, Bc, st, skip_embed);
     if (rc) return rc;
     PostArgs p{};
     fill_post(h, p, cond, s, off, Bc);
-    p.logits = h->logits;
+    p.logits = ws.logits;
     p.ldl = h->Cp;
     p.tokens = tin + (size_t)off * h->S;
     p.t_post = t_post;
@@ -108,7 +106,7 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
       if (rel) p.pad_disable = 1;
       p.tokens_out = tout + (size_t)off * h->S;
       if (embed_next) {  // (one chunk per call: run_loop_body)
-        p.x_next = h->P; p.emb = h->emb; p.pos = h->pos; p.D = h->D; p.ldx = h->D;
+        p.x_next = ws.P; p.emb = h->emb; p.pos = h->pos; p.D = h->D; p.ldx = h->D;
       }
       if (tie_row >= 0 && h->tie_rel > 0.f && h->tie_flags && s->kind == LDM_SAMPLE_DETERMINISTIC) {
         p.tie_flags = h->tie_flags + (size_t)tie_row * h->cfg.max_batch + rng_layout_off + off;
@@ -125,7 +123,7 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
       q.pad_disable = 1;
       q.tokens_out = tout + (size_t)off * h->S;
       if (embed_next) {
-        q.x_next = h->P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
+        q.x_next = ws.P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
       }
       RelArgs a{};
       a.cond_seq = cond->d_cond_seq + (size_t)off * h->S;
@@ -134,11 +132,11 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
       launch_relation_step(q, a, st);
       continue;
     }
-    if (!h->rel_logp) return h->fail(-5, "cond=relation: the three-launch step has no log-probability buffer (check_relation)");
+    if (!ws.rel_logp) return h->fail(-5, "cond=relation: the three-launch step has no log-probability buffer (check_relation)");
     {
       PostArgs q = p;
       q.pad_disable = 0;  // applied after the adjustment, below
-      q.logp_out = h->rel_logp;
+      q.logp_out = ws.rel_logp;
       q.logp_tm = 1;  // (the handle's own buffer: token-major, a token's classes contiguous)
       q.tokens_out = nullptr;
       ldm_handle::Scope sc(h, st, "posterior", 0, (double)Bc * h->S * (h->Cp * 4 + h->C * 4));
@@ -146,7 +144,7 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
     }
     {
       RelArgs a{};
-      a.logp = h->rel_logp;
+      a.logp = ws.rel_logp;
       a.logp_tm = 1;
       a.cond_seq = cond->d_cond_seq + (size_t)off * h->S;
       fill_rel(h, a, rel, rel_layout_off + off, Bc);
@@ -159,13 +157,13 @@ static int step_all(ldm_handle* h, const int32_t* tin, int32_t* tout, int t_mode
       q.strong = nullptr;  // already imposed on rel_logp
       q.weak = nullptr;
       q.pad_disable = 1;
-      q.logp_in = h->rel_logp;
+      q.logp_in = ws.rel_logp;
       q.logp_tm = 1;
       q.tokens_out = tout + (size_t)off * h->S;
       q.step = step;
       q.layout_off = (int)(rng_layout_off + off);
       if (embed_next) {  // the next step's embedding rows, as in the fused launch above
-        q.x_next = h->P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
+        q.x_next = ws.P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
       }
       ldm_handle::Scope sc(h, st, "pad_disable_sample", 0, (double)Bc * h->S * (h->C * 4 + 8));
       launch_posterior_sample(q, st);
@@ -268,7 +266,7 @@ extern "C" int ldm_sample_step(ldm_handle* h, const int32_t* d_tokens_in, int32_
   if (loop_fusable(h, rel)) {
     const int32_t tm = t_model, tp = t_post;
     if ((rc = run_loop_fused(h, d_tokens_in, d_tokens_out, cond, rel, &tm, &tp, 1, s, step, B, nullptr, 0, st))) return rc;
-  } else if ((rc = step_all(h, d_tokens_in, d_tokens_out, t_model, t_post, cond, rel, 0, s, step, B, 0, st, false, false, 0))) {
+  } else if ((rc = step_all(h, h->ws[0], d_tokens_in, d_tokens_out, t_model, t_post, cond, rel, 0, s, step, B, 0, st, false, false, 0))) {
     return rc;
   }
   HIP_OK(h, hipGetLastError());
@@ -284,7 +282,8 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
   const size_t S = h->S;
   // BALANCED chunks (r06): a call of B layouts needs ceil(B / chunk) passes; they share the layouts evenly — 300 layouts are 150 + 150, not 256 + 44
   // (the 44-layout pass kept 212 of 256 compute units idle for as long as the full one; a call's two passes also overlap on the lanes when each
-  // fills only part of the chip: same-box split 1 012 -> 1 105, hybrid 1 818 -> 2 011 layouts/s at B = 300; + 6 % / + 1 % at B = 400).  Tokens do not depend on the cut (tests/test_config34_shapes.py).
+  // fills only part of the chip: same-box split 1 012 -> 1 105, hybrid 1 818 -> 2 011 layouts/s at B = 300; + 6 % / + 1 % at B = 400).  Tokens do not depend on the cut
+  // (B = 300 as 150 + 150: tests/test_hip_parity.py test_split_mode_loop_properties, tests/test_r04_parity.py test_relation_in_the_loop_kernel_equals_the_per_step_path).
   // Only where the remainder is small: with a remainder of >= 3/4 of a chunk the uneven cut is 2 % FASTER for the short hybrid launches (488 = 256 + 232: 2 142
   // against 2 093 for 244 + 244 — passes of unequal length drift against each other on the lanes instead of running in lock-step; profiles/r06_call16_17_25_*).
   const int n_pass = (B + h->chunk - 1) / h->chunk;
@@ -292,7 +291,7 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
   const int cb = (h->balanced_chunks && n_pass > 1 && 4 * rem < 3 * h->chunk) ? (B + n_pass - 1) / n_pass : h->chunk;
   const int first = lane < 0 ? 0 : lane * cb;
   const int stride = lane < 0 ? cb : h->n_lanes * cb;
-  h->activate(lane < 0 ? 0 : lane);
+  Workspace& ws = h->ws[lane < 0 ? 0 : lane];
   for (int off = first; off < B; off += stride) {
     const int Bc = std::min(cb, B - off);
     ldm_cond cc{};
@@ -308,7 +307,7 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
     // step i + 1's embedding itself (no separate embedding launch inside the loop)
     const bool fuse_embed = h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6;
     for (int i = 0; i < n_steps; ++i) {
-      int rc = step_all(h, cur, nxt, t_model[i], t_post[i], cond ? &cc : nullptr, rel, off, s, i, Bc, off, st,
+      int rc = step_all(h, ws, cur, nxt, t_model[i], t_post[i], cond ? &cc : nullptr, rel, off, s, i, Bc, off, st,
                         fuse_embed && i > 0, fuse_embed && i + 1 < n_steps, i);
       if (rc) return rc;
       if (d_inter)

@@ -447,9 +447,11 @@ def test_full_batch_512_properties(cuda):
 
 def test_split_mode_loop_properties(cuda):
     """The split mode (fp16 x 3 GEMMs on 256 x 256 tiles, r04) on a batch that does not fill its last chunk or its last
-    row tile (B = 300: chunks of 256 + 44 layouts = 32 000 + 5 500 rows): hipGraph replay == eager launches, the tokens of
-    layout i do not depend on how the batch is cut (rows past M feed products that are never stored), determinism, and a
-    teacher-forced greedy step == the exact engine's at B = 300."""
+    row tile (B = 300: the loop's balanced cut, two passes of 150 layouts = 18 750 rows, one per lane — ldm_loop.cpp
+    run_loop_body; the single step at the end: 256 + 44 layouts = 32 000 + 5 500 rows): hipGraph replay == eager launches,
+    the tokens of layout i do not depend on how the batch is cut (100 + 200 layouts in two calls against 150 + 150 in one;
+    rows past M feed products that are never stored), determinism, and a teacher-forced greedy step == the exact engine's
+    at B = 300."""
     spec = SP.RICO25
     B = 300
     e = engine("rico25", "split", max_batch=512)
