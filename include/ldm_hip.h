@@ -284,6 +284,51 @@ int ldm_relation_violation_dense(const void* d_bbox, int box_f64, const uint8_t*
                                  const int32_t* d_dst, const int32_t* d_attr, const int64_t* d_first_node, int n_graph,
                                  int n_edge, float* d_out, int32_t* d_edge_out, int32_t* d_err, void* stream);
 
+/* ---- cond= inputs from raw layouts (tokenizer.encode, get_cond and the relation transforms) --------------------------------
+ * helpers/layout_tokenizer.py:208-253 + helpers/bbox_tokenizer.py:84-115 (encode), helpers/task.py:27-151 (get_cond),
+ * data/util.py:111-177 (AddCanvasElement + AddRelationConstraints, use_v1=False) for the LayoutDM tokenizer configuration
+ * ldm_decode_layouts assumes (c-x-y-w-h, stacked x-y-w-h vocabulary, [pad, mask], pad_until_max, no bos / eos).  Device
+ * pointers in and out, no handle, the current device.  Layouts are dense: d_bbox (B,E,4) float32 / float64 by box_f64 (16- /
+ * 32-byte aligned), d_label (B,E) int64, d_mask (B,E) uint8 (1 = element; a prefix of every row), 1 <= E <= 32.
+ * *d_err (int32, zeroed by the call): bit 0 = a mask that is not a prefix, bit 1 = a non-finite coordinate on a valid element,
+ * bit 2 = a label outside [0, n_category) on a valid element.  Returns 0, -1 (bad argument: nothing launched) or -2 (launch
+ * failed).
+ * Own draws use Philox4x32-10 keyed by (seed, first_layout + layout index, purpose, slot): the result does not depend on how
+ * a batch is cut.  They follow the reference's DISTRIBUTIONS, not its random / torch streams. */
+#define LDM_QUANT_LINEAR 0
+#define LDM_QUANT_PERCENTILE 1
+#define LDM_QUANT_KMEANS 2
+#define LDM_COND_NONE 0        /* the plain tokenizer.encode ("gt") */
+#define LDM_COND_C 1
+#define LDM_COND_CWH 2
+#define LDM_COND_PARTIAL 3
+#define LDM_COND_REFINEMENT 4
+#define LDM_COND_RELATION 5
+/* encode + the cond rule in one pass.  quant / d_centres: LDM_QUANT_LINEAR with NULL, else (4,n_bin) float64 sorted centres in
+ * x, y, w, h order (n_bin <= 128); kmeans picks the nearest centre by |float32(x) - c| in float64, lowest index on a tie.
+ * d_keep (B,E) uint8: the per-element keep mask of LDM_COND_PARTIAL, or NULL = drawn (k = randint(1, vmax) if vmax > 1 else 1,
+ * vmax = int((n - 1) * 0.3), then a uniform k-subset of the n elements).  d_noise (B,E,4) float32: the noise LDM_COND_REFINEMENT
+ * adds to the boxes, or NULL = drawn (iid normal, sigma 0.1); d_noise_out (B,E,4) or NULL receives what was added.
+ * d_seq (B,5E) int32, d_cond_mask (B,5E) uint8, d_seq_orig (B,5E) int32 (refinement; else may be NULL), d_num_element (B)
+ * int32 or NULL. */
+int ldm_encode_cond(const void* d_bbox, int box_f64, const int64_t* d_label, const uint8_t* d_mask, int B, int E,
+                    int n_category, int n_bin, int quant, const double* d_centres, int rule, const uint8_t* d_keep,
+                    const float* d_noise, uint64_t seed, uint64_t first_layout, int32_t* d_seq, uint8_t* d_cond_mask,
+                    int32_t* d_seq_orig, int32_t* d_num_element, float* d_noise_out, int32_t* d_err, void* stream);
+/* cond["batch_w_canvas"]: node 0 of every layout is the canvas box (0.5, 0.5, 1, 1) with label 0, element labels + 1; for every
+ * pair i < j in combinations order, attr = 1 << size | 1 << loc with UNKNOWN for a relation that is not sampled; an edge exists
+ * where attr != both-unknown.  d_selection (B,2,E+1,E+1) uint8 [kind: 0 size, 1 loc][i][j] != 0 = sampled, or NULL = drawn:
+ * exactly int(2 * C(n + 1, 2) * edge_ratio) of a layout's (kind, pair) candidates, uniformly without replacement.
+ * With P = (E + 1) * E / 2: d_work (B, 2 P + 1) int32 workspace; the per-layout CSR ldm_relation_update and
+ * ldm_relation_violation take: d_edge_off (B+1), d_src / d_dst / d_attr (capacity B * P) int32, d_first_node (B) int64; the
+ * nodes (capacity B * (E + 1) rows): d_node_box (rows,4) in the boxes' dtype, d_node_label / d_node_batch int64, d_canvas
+ * uint8; d_totals (2) int32 = {edges, nodes} actually written.  B >= 1. */
+int ldm_relation_graph(const void* d_bbox, int box_f64, const int64_t* d_label, const uint8_t* d_mask, int B, int E,
+                       int n_category, const uint8_t* d_selection, double edge_ratio, uint64_t seed, uint64_t first_layout,
+                       int32_t* d_work, int32_t* d_edge_off, int32_t* d_src, int32_t* d_dst, int32_t* d_attr,
+                       int64_t* d_first_node, void* d_node_box, int64_t* d_node_label, int64_t* d_node_batch,
+                       uint8_t* d_canvas, int32_t* d_totals, int32_t* d_err, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------- */
 /* average device time (ms) of the most recent ldm_sample_loop, measured with HIP events on the
  * stream it ran on; blocks until that loop has finished. */

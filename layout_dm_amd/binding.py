@@ -35,6 +35,8 @@ EXPORTS = (
     "ldm_eval_average_iou", "ldm_eval_docsim", "ldm_eval_max_iou_pairs",
     # relation violation score (bound in layout_dm_amd/metrics.py)
     "ldm_relation_violation", "ldm_relation_violation_dense",
+    # cond= inputs from raw layouts (bound in layout_dm_amd/task.py)
+    "ldm_encode_cond", "ldm_relation_graph",
 )
 
 
@@ -134,6 +136,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     graph = [vp, C.c_int64, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]  # canvas, n_nodes, CSR, first_node, counts, out, edge_out, err, stream
     lib.ldm_relation_violation.argtypes = [vp, i32, C.c_int64] + graph
     lib.ldm_relation_violation_dense.argtypes = [vp, i32, vp, i32, i32, vp] + graph
+    lib.ldm_encode_cond.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]
+    lib.ldm_relation_graph.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, C.c_double, u64, u64] + [vp] * 13
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int
@@ -361,7 +365,13 @@ class Engine:
         from .relation import graph_to_csr
 
         B = int(n_graph_total)
-        off, src_l, dst_l, ea = graph_to_csr(graph, B)
+        csr = getattr(graph, "csr", None)
+        if csr is not None and csr["edge_off"].numel() == B + 1:
+            # task.relation_graph built the graph in this form on the device: nothing to rebuild.  The CSR is taken as it is,
+            # without graph_to_csr's checks: task.RelationGraph keeps it and its DataBatch view read-only for that reason
+            off, src_l, dst_l, ea = csr["edge_off"], csr["src"], csr["dst"], csr["attr"]
+        else:
+            off, src_l, dst_l, ea = graph_to_csr(graph, B)
         dev = self.device
         keep = [off.to(dev), src_l.to(dev), dst_l.to(dev), ea.to(dev),
                 torch.as_tensor(centres, dtype=torch.float64).float().reshape(4, self.n_bin).contiguous().to(dev)]

@@ -207,6 +207,44 @@ void launch_relation_violation(const void* bbox, int box_f64, int64_t n_rows, co
 // bbox (B,S,4) + mask (B,S) of ldm_decode_layouts, a canvas row in front of every layout; row_start (B+1) i32 is filled
 void launch_relation_violation_dense(const void* bbox, int box_f64, const uint8_t* mask, int B, int S, int32_t* row_start,
                                      const ViolationGraph& g, float* out, int32_t* edge_out, int32_t* err, hipStream_t st);
+// raw layouts -> cond= inputs (kernels_cond.hip); arguments checked by the C-ABI (ldm_cond_api.cpp)
+struct CondEncodeArgs {
+  const void* bbox;            // (B,E,4) float32 / float64 (xc, yc, w, h)
+  int box_f64;
+  const int64_t* label;        // (B,E)
+  const uint8_t* mask;         // (B,E) 1 = element
+  int B, E, n_category, n_bin, quant, rule, pad_id, mask_id;
+  const double* centres;       // (4,n_bin) or nullptr (linear bins)
+  const uint8_t* keep;         // (B,E) partial keep mask, or nullptr: drawn
+  const float* noise;          // (B,E,4) refinement noise, or nullptr: drawn
+  uint64_t seed, first_layout;
+  int32_t* seq;                // (B,5E)
+  uint8_t* cond_mask;          // (B,5E)
+  int32_t* seq_orig;           // (B,5E), refinement
+  int32_t* num_element;        // (B) or nullptr
+  float* noise_out;            // (B,E,4) the noise that was added, or nullptr
+  int32_t* err;
+};
+void launch_encode_cond(const CondEncodeArgs& a, hipStream_t st);
+struct CondGraphArgs {
+  const void* bbox;
+  int box_f64;
+  const int64_t* label;
+  const uint8_t* mask;
+  int B, E, n_category;
+  const uint8_t* selection;    // (B,2,E+1,E+1) [kind][i][j] != 0: the relation is sampled, or nullptr: drawn
+  double edge_ratio;
+  uint64_t seed, first_layout;
+  int32_t* work;               // (B, 2 P + 1), P = (E+1) E / 2: per layout {count, attr[P], (i << 8 | j)[P]}
+  int32_t *edge_off, *src, *dst, *attr;   // CSR: (B+1), capacity B P each
+  int64_t* first_node;         // (B)
+  void* node_box;              // (B (E+1), 4) capacity, the boxes' dtype
+  int64_t *node_label, *node_batch;
+  uint8_t* canvas;
+  int32_t* totals;             // {edges, nodes}
+  int32_t* err;
+};
+void launch_relation_graph(const CondGraphArgs& a, hipStream_t st);
 // ids -> {bbox, label, mask} (kernels_decode.hip); centres: [4][n_bin] f64 cluster centres or nullptr (linear bins)
 void launch_decode_layouts(const int32_t* tokens, int B, int E, int A, int n_category, int n_bin,
                            const double* centres, int box_f64, void* bbox, int64_t* label, uint8_t* mask,

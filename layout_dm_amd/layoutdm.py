@@ -235,6 +235,27 @@ class LayoutDM:
         return inner.sample(batch_size=batch_size, cond=cond, sampling_cfg=sampling_cfg,
                             get_intermediate_results=get_intermediate_results, **kwargs)
 
+    # ---- raw layouts in: layout_dm_amd/task.py -------------------------------------------------------------
+    def encode(self, layouts: Dict) -> Dict[str, torch.Tensor]:
+        """tokenizer.encode of {"bbox", "label", "mask"} on the GPU (task.encode): {"seq" int64, "mask" bool}."""
+        from . import task
+
+        return task.encode(self.tokenizer, layouts["bbox"], layouts["label"], layouts["mask"])
+
+    def sample_from_layouts(self, layouts: Dict, cond_type: str, sampling_cfg=None, *, keep=None, noise=None, selection=None,
+                            edge_ratio: float = 0.1, cond_seed: Optional[int] = None, first_layout: int = 0, **kwargs):
+        """get_cond (task.get_cond, kernels_cond.hip) -> refinement prior -> sampling -> decode, the tokens staying on the
+        device: `sample(batch_size=B, cond=task.get_cond(layouts, ...), ...)` with the layouts moved to the GPU first.
+        cond_seed keys the builder's own draws; every other keyword (seed, ...) goes to sample()."""
+        from . import task
+
+        dev = self.model.module.engine.device
+        on_dev = {k: torch.as_tensor(layouts[k]).to(dev) for k in ("bbox", "label", "mask")}
+        cond = task.get_cond(on_dev, self.tokenizer, cond_type, keep=keep, noise=noise, selection=selection,
+                             edge_ratio=edge_ratio, seed=cond_seed, first_layout=first_layout)
+        return self.sample(batch_size=on_dev["bbox"].shape[0], cond=cond, sampling_cfg=sampling_cfg, cond_type=cond_type,
+                           first_layout=first_layout, **kwargs)
+
     def _device_decode_centres(self):
         if getattr(self, "_decode_plan", None) is None:
             self._decode_plan = device_decode_plan(self.tokenizer)
