@@ -85,7 +85,11 @@ typedef struct {
 /* sampling_cfg of the reference (helpers/sampling.py dataclasses) */
 typedef struct {
   int32_t kind;      /* LDM_SAMPLE_* */
-  float temperature; /* logits / temperature (stochastic kinds only) */
+  float temperature; /* logits / temperature (stochastic kinds only), > 0.  ldm_sample_step / ldm_sample_loop draw on a
+                      * token's own sub-vocabulary only and return an error when the classes outside it — log(1e-30)
+                      * each, divided by the temperature like every class — would hold more than 2^-24 of the mass:
+                      * n_class * exp(log(1e-30) / temperature) > 2^-24, i.e. temperature > 69.08 / log(2^24 * n_class)
+                      * (3.19 for 155 classes).  ldm_sample_tokens draws over the full vocabulary: any temperature > 0. */
   float top_p;       /* LDM_SAMPLE_TOP_P */
   int32_t top_k;     /* LDM_SAMPLE_TOP_K */
 } ldm_sampler;

@@ -322,6 +322,7 @@ int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, 
 void fill_post(ldm_handle* h, ldm::PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off, int Bc);
 int check_ready(ldm_handle* h, int B);
 int check_sampler(ldm_handle* h, const ldm_sampler* s);
+int check_live_temperature(ldm_handle* h, const ldm_sampler* s);  // step / loop only (ldm_loop.cpp)
 int set_rng(ldm_handle* h, uint64_t seed, uint64_t first_layout, hipStream_t st);
 void fill_rel(ldm_handle* h, ldm::RelArgs& a, const ldm_relation* rel, size_t layout_off, int Bc);
 bool loop_fusable(const ldm_handle* h, const ldm_relation* rel);

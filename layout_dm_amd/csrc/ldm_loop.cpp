@@ -44,6 +44,24 @@ int ldm_host::check_sampler(ldm_handle* h, const ldm_sampler* s) {
   return 0;
 }
 
+// ldm_sample_step / ldm_sample_loop draw on a token's LIVE classes only (SlotMap<., ., LIVE> of ldm_post_token.h: the tail
+// of the stack kernel and posterior_sample_k's 16-lane form) and skip strong-masked positions.  The reference divides the
+// dead classes' log(1e-30) by the temperature like every other class (helpers/sampling.py:90), so together they hold up to
+// C * exp(log(1e-30) / T) of the mass.  While that stays within the 2^-24 resolution of the draw's uniform the forms agree
+// draw for draw; above (T > 3.19 for 155 classes) the live-class forms would sample another distribution than the
+// reference and than ldm_sample_tokens' full-vocabulary form: refused, never approximated.
+int ldm_host::check_live_temperature(ldm_handle* h, const ldm_sampler* s) {
+  if (s->kind == LDM_SAMPLE_DETERMINISTIC) return 0;
+  const double log_eps = std::log(1e-30);  // util.py:8
+  const double dead_mass = (double)h->C * std::exp(log_eps / (double)s->temperature);
+  if (dead_mass > std::ldexp(1.0, -24))
+    return h->fail(-1, "temperature %g puts %.3g of the mass on classes outside a token's sub-vocabulary (more than 2^-24): "
+                       "the step / loop draw on the live classes only and must be given temperature <= %.4f for %d classes",
+                   (double)s->temperature, dead_mass,
+                   -log_eps / std::log(std::ldexp(1.0, 24) * (double)h->C), h->C);
+  return 0;
+}
+
 static int check_relation(ldm_handle* h, const ldm_relation* rel, const ldm_cond* cond, int B) {
   if (!rel) return 0;
   if (!cond || !cond->d_cond_seq) return h->fail(-1, "cond=relation needs cond->d_cond_seq (the conditioned sequence)");
@@ -255,6 +273,7 @@ extern "C" int ldm_sample_step(ldm_handle* h, const int32_t* d_tokens_in, int32_
   int rc = check_ready(h, B);
   if (rc) return rc;
   if ((rc = check_sampler(h, s))) return rc;
+  if ((rc = check_live_temperature(h, s))) return rc;
   if (!d_tokens_in || !d_tokens_out) return h->fail(-1, "null argument");
   ON_DEVICE(h);
   if ((rc = check_relation(h, rel, cond, B))) return rc;
@@ -328,6 +347,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
   int rc = check_ready(h, B);
   if (rc) return rc;
   if ((rc = check_sampler(h, s))) return rc;
+  if ((rc = check_live_temperature(h, s))) return rc;
   if (!d_tokens_inout || !h_t_model || !h_t_post || n_steps < 1) return h->fail(-1, "bad argument");
   for (int i = 0; i < n_steps; ++i)
     if (h_t_model[i] < 0 || h_t_model[i] >= h->T || h_t_post[i] < 0 || h_t_post[i] >= h->T)

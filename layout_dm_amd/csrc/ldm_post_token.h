@@ -17,8 +17,11 @@
 //        DppGroup<64>      NL = 64  one wavefront per token over the FULL vocabulary: the parity hooks that read or write
 //                                   (B, C, S) log-probability tensors (ldm_posterior / ldm_sample_tokens)
 //   M  (slot map)     SlotMap<NL, NJ, LIVE>: slot j of lane l is candidate l + NL j, in class order; LIVE = the candidates
-//                     are the token's live classes only (dead classes carry 1e-30 of the mass each: leaving them out of
-//                     the draw moves a CDF edge by < 1e-28 relative), else all C classes.
+//                     are the token's live classes only, else all C classes.  A dead class carries exp(log(1e-30) / T) of
+//                     the mass at temperature T (1e-30 at T = 1): leaving the dead classes out of the draw is exact to
+//                     the 2^-24 resolution of the uniform only while C exp(log(1e-30) / T) <= 2^-24.  The callers of
+//                     the LIVE forms enforce that (ldm_loop.cpp check_live_temperature: T <= 3.19 for 155 classes);
+//                     the full-vocabulary form takes any T > 0.
 //
 // Pure C++ apart from the DPP policy: no HIP types here.
 #pragma once
@@ -232,10 +235,11 @@ struct Draw {
 };
 
 // A strong-masked position (base.py:245-251) carries log-probability 0 on its conditioned token and log(1e-30) on every
-// other class: argmax returns the conditioned token, and so does every stochastic draw this sampler can make — the other
-// classes hold < 2e-28 of the mass, below the 2^-24 resolution of the uniform (and gumbel noise spans < 20 of the 69 nats
-// between them).  Callers skip the posterior and the draw for such tokens; the tokens are identical either way
-// (tests/test_hip_parity.py::test_strong_mask_shortcut_is_an_identity).
+// other class: argmax returns the conditioned token, and so does every stochastic draw this sampler can make at the
+// temperatures its callers admit (ldm_loop.cpp check_live_temperature: the other classes together hold
+// C exp(log(1e-30) / T) <= 2^-24 of the mass, the resolution of the uniform; < 2e-28 at T = 1, where gumbel noise spans
+// < 20 of the 69 nats between them).  Callers skip the posterior and the draw for such tokens; the tokens are identical
+// either way (tests/test_hip_parity.py::test_strong_mask_shortcut_is_an_identity).
 LDM_PT_HD bool strong_shortcut(const TokenArgs& a) { return a.strong && a.cond_tok >= 0 && a.cond_tok < a.n_class; }
 
 // ---- top-k / top-p: walk the candidates o in class order; for the class of each slot j accumulate the probability

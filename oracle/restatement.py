@@ -265,6 +265,35 @@ def token_uniforms(seed: int, first_layout: int, B: int, S: int, step: int, n: i
     return u[..., :n]
 
 
+def token_gumbel_uniforms(seed: int, first_layout: int, B: int, S: int, step: int, C: int) -> np.ndarray:
+    """Per-class uniforms of the gumbel sampler's noise, (B,C,S) float32: class c of token (layout, pos) at reverse step
+    `step` reads component c & 3 of the Philox block whose counter word 0 is pos | (1 + (c >> 2)) << 16; words 1-3 and
+    the key are those of `token_uniforms` (whose draw uniform is component 0 of the block with word 0 = pos, so the
+    two never share a word while pos < 2^16).  Restated in uint64 arithmetic, independent of the kernel's."""
+    Q = (C + 3) // 4
+    lay = (np.arange(B, dtype=np.uint64) + np.uint64(first_layout))
+    ctr = np.zeros((B, S, Q, 4), np.uint64)
+    pos = np.arange(S, dtype=np.uint64)[None, :, None]
+    blk = (np.arange(Q, dtype=np.uint64) + np.uint64(1))[None, None, :]
+    ctr[..., 0] = pos | (blk << np.uint64(16))
+    ctr[..., 1] = np.uint64(step)
+    ctr[..., 2] = (lay & np.uint64(0xFFFFFFFF))[:, None, None]
+    ctr[..., 3] = (lay >> np.uint64(32))[:, None, None]
+    key = np.zeros((B * S * Q, 2), np.uint64)
+    key[:, 0] = np.uint64(seed & 0xFFFFFFFF)
+    key[:, 1] = np.uint64((seed >> 32) & 0xFFFFFFFF)
+    r = philox4x32(ctr.reshape(-1, 4), key).reshape(B, S, Q * 4)[..., :C]      # class c = 4 * block + component
+    u = ((r >> np.uint32(9)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -23)
+    return np.ascontiguousarray(u.transpose(0, 2, 1))
+
+
+def gumbel_logits(logp: torch.Tensor, cfg: dict, gumbel_uniforms) -> torch.Tensor:
+    """helpers/sampling.py:90,113-116 on explicit uniforms, float32: logits / temperature + gumbel noise."""
+    u = torch.as_tensor(gumbel_uniforms, dtype=torch.float32)
+    assert u.shape == logp.shape
+    return logp.float() / cfg.get("temperature", 1.0) + (-torch.log(-torch.log(u + 1e-30) + 1e-30))
+
+
 def filter_logits(logp: torch.Tensor, cfg: dict) -> torch.Tensor:
     """The non-random part of helpers/sampling.py:81-116: temperature, top-k, top-p
     (incl. the quirk that the threshold-crossing class is dropped too, l.101-108)."""
@@ -296,14 +325,17 @@ def sample_probs(logp: torch.Tensor, cfg: dict) -> torch.Tensor:
 
 
 def sample_tokens(logp: torch.Tensor, cfg: dict, uniforms: Optional[np.ndarray] = None,
-                  generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                  generator: Optional[torch.Generator] = None, gumbel_uniforms=None) -> torch.Tensor:
     """helpers/sampling.py:81-130.  deterministic -> argmax over classes (first max).
     Stochastic: with `uniforms` (B,S) the draw is the inverse-CDF rule of OUR kernel
     (smallest class c with cumsum(p)[c] > u * sum(p)), else torch.multinomial like the
-    reference.  Returns (B,S) int64."""
+    reference.  gumbel: with `gumbel_uniforms` (B,C,S) (token_gumbel_uniforms) the noise is built from them; without,
+    and with `uniforms`, NO noise is added (the draw is then plain `random`).  Returns (B,S) int64."""
     if cfg["name"] == "deterministic":
         return torch.argmax(logp, dim=1)
-    if cfg["name"] == "gumbel" and uniforms is None:
+    if cfg["name"] == "gumbel" and gumbel_uniforms is not None:
+        probs = F.softmax(gumbel_logits(logp, cfg, gumbel_uniforms), dim=1)
+    elif cfg["name"] == "gumbel" and uniforms is None:
         u = torch.rand(logp.shape, generator=generator)
         logp = logp / cfg.get("temperature", 1.0) + (-torch.log(-torch.log(u + 1e-30) + 1e-30))
         probs = F.softmax(logp, dim=1)
@@ -329,7 +361,7 @@ def timestep_list(T_model: int, T_eval: int):
 
 
 def single_step(W, spec, tokens, t, cfg, cond=None, skip_step: int = 0, uniforms=None, generator=None,
-                dtype=torch.float32, return_all=False, q_type: str = "constrained"):
+                dtype=torch.float32, return_all=False, q_type: str = "constrained", gumbel_uniforms=None):
     """_sample_single_step (categorical_diffusion/base.py:205-291) in token form."""
     logits = denoiser_logits(W, spec, tokens, t, dtype=dtype).float()
     log_x0 = predict_start_from_logits(logits)
@@ -341,7 +373,7 @@ def single_step(W, spec, tokens, t, cfg, cond=None, skip_step: int = 0, uniforms
         noise_t = noise_t - skip_step
     logp = q_posterior(W, spec, log_x0, tokens, noise_t, q_type=q_type)
     logp = apply_cond(spec, logp, cond, t)          # the relation update sees the MODEL timestep (base.py:262)
-    nxt = sample_tokens(logp, cfg, uniforms=uniforms, generator=generator)
+    nxt = sample_tokens(logp, cfg, uniforms=uniforms, generator=generator, gumbel_uniforms=gumbel_uniforms)
     if return_all:
         return nxt, logits, logp
     return nxt
@@ -349,11 +381,13 @@ def single_step(W, spec, tokens, t, cfg, cond=None, skip_step: int = 0, uniforms
 
 def sample_loop(W, spec: ModelSpec, batch_size: int, cfg: dict, cond: Optional[dict] = None,
                 seed: Optional[int] = None, first_layout: int = 0, generator=None,
-                dtype=torch.float32, get_intermediate_results=False, q_type: str = "constrained"):
+                dtype=torch.float32, get_intermediate_results=False, q_type: str = "constrained",
+                gumbel_noise: bool = False):
     """BaseMaskAndReplaceDiffusion.sample (categorical_diffusion/base.py:293-371).
     With `seed` the stochastic draws use the Philox inverse-CDF rule of the HIP kernel
     (keyed by global layout index => independent of batch split); otherwise
-    torch.multinomial like the reference."""
+    torch.multinomial like the reference.  gumbel_noise (with `seed`, sampler gumbel): add the kernel's per-class
+    Philox noise of every step (token_gumbel_uniforms); off, a seeded gumbel loop draws without noise, as before."""
     T_eval = cfg.get("num_timesteps", spec.n_step)
     steps = timestep_list(spec.n_step, T_eval)
     if cond:
@@ -368,11 +402,13 @@ def sample_loop(W, spec: ModelSpec, batch_size: int, cfg: dict, cond: Optional[d
     prev = spec.n_step
     inter = []
     for i, t in enumerate(steps):
-        u = None
+        u = gu = None
         if seed is not None and cfg["name"] != "deterministic":
             u = token_uniforms(seed, first_layout, batch_size, spec.seq_len, i)[..., 0]
+            if gumbel_noise and cfg["name"] == "gumbel":
+                gu = token_gumbel_uniforms(seed, first_layout, batch_size, spec.seq_len, i, spec.n_class)
         tokens = single_step(W, spec, tokens, t, cfg, cond, skip_step=prev - t - 1, uniforms=u,
-                             generator=generator, dtype=dtype, q_type=q_type)
+                             generator=generator, dtype=dtype, q_type=q_type, gumbel_uniforms=gu)
         prev = t
         if get_intermediate_results:
             inter.append(tokens.clone())

@@ -230,12 +230,40 @@ def test_sampler_statistics_match_reference_distribution(cuda):
     row[live] = torch.log_softmax(torch.randn(len(live), generator=g) * 1.5, 0)
     logp = row.view(1, -1, 1).repeat(B, 1, spec.seq_len).contiguous()
     for cfg in ({"name": "random", "temperature": 1.0}, {"name": "top_p", "top_p": 0.8, "temperature": 1.0},
-                {"name": "gumbel", "temperature": 1.0}):
+                {"name": "gumbel", "temperature": 1.0}, {"name": "gumbel", "temperature": 0.7}):
         out = e.sample_tokens(logp, cfg, seed=3, step=7).cpu().long().ravel().numpy()
         if cfg["name"] == "gumbel":
-            # gumbel noise THEN multinomial (sampling.py:112-127): E[softmax(l+g)] has no closed form;
-            # check support + that it is more spread than the plain distribution's mode
+            # gumbel noise THEN multinomial (sampling.py:112-127): the class probabilities are E[softmax(l / T + g)], which
+            # has no closed form.  Estimated on the CPU with torch.rand and the reference's own expression (sampling.py:113-116),
+            # averaging the softmax over 2e6 noise samples (two such estimates differ by a chi-square equivalent of 0.4 at
+            # n = 64 000) — independent of the Philox restatement.  T = 0.7 tells l / T + g from (l + g) / T.
             assert np.isin(out, live.numpy()).all()
+            T = cfg["temperature"]
+            gen = torch.Generator().manual_seed(2024)
+            acc = torch.zeros(spec.n_class, dtype=torch.float64)
+            n_chunk, chunk = 20, 100_000
+            for _ in range(n_chunk):
+                uniform = torch.rand(chunk, spec.n_class, generator=gen)
+                noise = -torch.log(-torch.log(uniform + 1e-30) + 1e-30)
+                acc += torch.softmax(row.view(1, -1) / T + noise, dim=1).double().sum(0)
+            p = (acc / (n_chunk * chunk)).numpy()
+            stat = lambda q: _chi2(out, q, spec.n_class)
+            chi2, dof, cnt_rest, n_rest = stat(p)
+            plain = R.sample_probs(logp[:1, :, :1], {"name": "random", "temperature": T})[0, :, 0].numpy().astype(np.float64)
+            chi2_plain, dof_plain, _, _ = stat(plain)
+            print(f"[gumbel T={T}] chi2 against E[softmax(l/T+g)]: {chi2:.1f} (dof {dof}, bound "
+                  f"{dof + 6 * np.sqrt(2 * dof) + 10:.1f}); against the noise-free probabilities: {chi2_plain:.1f}")
+            assert cnt_rest <= 5 * n_rest + 10
+            assert chi2 < dof + 6 * np.sqrt(2 * dof) + 10, (cfg, chi2, dof)
+            # cancelled or missing noise would pass a support check: it must FAIL against the noise-free probabilities
+            assert chi2_plain > dof_plain + 6 * np.sqrt(2 * dof_plain) + 10, (cfg, chi2_plain)
+            # the noise and the draw of another step are independent of this one's: two steps agree as often as
+            # independent draws from p do, sum p_k^2, within the binomial 6 sigma of the 64 000 pairs
+            other = e.sample_tokens(logp, cfg, seed=3, step=8).cpu().long().ravel().numpy()
+            q = float((p ** 2).sum())
+            agree = float((out == other).mean())
+            print(f"[gumbel T={T}] steps 7 and 8 agree on {agree:.4f} of the draws; independent draws: {q:.4f}")
+            assert agree <= q + 6 * np.sqrt(q * (1 - q) / out.size), (agree, q)
             continue
         p = R.sample_probs(logp[:1, :, :1], cfg)[0, :, 0].numpy().astype(np.float64)
         cnt = np.bincount(out, minlength=spec.n_class).astype(np.float64)
@@ -245,6 +273,14 @@ def test_sampler_statistics_match_reference_distribution(cuda):
         dof = keep.sum() - 1
         assert cnt[~keep].sum() <= 5 * (~keep).sum() + 10
         assert chi2 < dof + 6 * np.sqrt(2 * dof) + 10, (cfg, chi2, dof)
+
+
+def _chi2(draws, p, n_class):
+    """Pearson statistic over the classes with n p >= 5 -> (chi2, dof, draws on the other classes, number of those)."""
+    cnt = np.bincount(draws, minlength=n_class).astype(np.float64)
+    n = cnt.sum()
+    keep = p * n >= 5
+    return (((cnt - n * p) ** 2)[keep] / (n * p)[keep]).sum(), keep.sum() - 1, cnt[~keep].sum(), (~keep).sum()
 
 
 # ----------------------------------------------------------------------------- fused step / loop

@@ -1,7 +1,8 @@
 """CPU: the per-token scalar tail of a reverse step (layout_dm_amd/csrc/ldm_post_token.h — log-softmax, constrained
 posterior on the token's sub-vocabulary, cond overrides, draw with the kernel's Philox stream), compiled for the host and
 run against the oracle on states of the REFERENCE's trajectories (tests/golden): greedy tokens, and stochastic draws on
-identical uniforms for random / top-k / top-p; gumbel for support and determinism.  This is the form in which one lane of
+identical uniforms for random / top-k / top-p, and for gumbel on identical per-class noise words; the same over the
+parameter edges of top-k / top-p / temperature (tests/_sampler_cases.py).  This is the form in which one lane of
 the stack kernel can finish a token behind the fused vocabulary head."""
 import os
 import shutil
@@ -15,6 +16,8 @@ import torch
 from oracle import restatement as R
 from oracle import spec as SP
 from oracle import synth
+
+import _sampler_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = {"deterministic": 0, "random": 1, "top_p": 2, "top_k": 3, "gumbel": 4}
@@ -161,3 +164,144 @@ def test_scalar_tail_gumbel_support_and_determinism(harness, tmp_path, golden_di
     assert torch.equal(a, b) and not torch.equal(a, c)
     for at in range(spec.n_attr):
         assert torch.isin(a[:, at::spec.n_attr], torch.as_tensor(spec.full_ids(at))).all()
+
+
+# ----------------------------------------------------------------------------- gumbel on explicit Philox noise
+GUMBEL_STATES = (3, 40, 80, 99)   # the states of test_scalar_tail_draws_equal_oracle_on_identical_uniforms
+
+
+def _gumbel_case(harness, tmp_path, golden_dir, cfg):
+    """[(host tokens, oracle logp, loop index)] over GUMBEL_STATES."""
+    spec, W = _weights("rico25")
+    g = np.load(os.path.join(golden_dir, "rico25_uncond_trajectory.npz"))
+    out = []
+    for i in GUMBEL_STATES:
+        t = int(g["steps"][i])
+        toks = torch.from_numpy(g["states_before"][i].astype(np.int64))
+        _, logits, logp = R.single_step(W, spec, toks, t, {"name": "deterministic"}, return_all=True)
+        out.append((_run(harness, tmp_path, spec, W, toks, t, logits, cfg, i, SC.SEED, SC.FIRST_LAYOUT), logp, i))
+    return out
+
+
+@pytest.mark.parametrize("temperature", [1.0, 0.7])
+def test_scalar_tail_gumbel_equals_oracle_on_identical_words(harness, tmp_path, golden_dir, temperature):
+    """gumbel: logp / T + noise(u_c) with the per-class uniforms of R.token_gumbel_uniforms (counter word 0 =
+    pos | (1 + c / 4) << 16, component c & 3), then the inverse CDF on the draw's own uniform: token for token against
+    R.single_step's draw, with the file's allowance for a CDF edge within fp32 rounding of u.  T = 0.7 tells
+    l / T + g from (l + g) / T."""
+    cfg = {"name": "gumbel", "temperature": temperature}
+    bad = total = 0
+    for out, logp, i in _gumbel_case(harness, tmp_path, golden_dir, cfg):
+        ref = SC.oracle_draw(logp, cfg, i)
+        assert SC.support(logp, cfg).gather(1, out[:, None, :]).all()
+        bad += int((out != ref).sum())
+        total += ref.numel()
+    print(f"[host form, gumbel T={temperature}] tokens differing from the oracle on identical words: {bad}/{total}")
+    assert bad <= 2, f"{bad}/{total}"
+
+
+@pytest.mark.parametrize("variant", ["no_noise", "shared_across_classes", "before_division", "draw_word_reused"])
+def test_scalar_tail_gumbel_parity_rejects_wrong_noise(harness, tmp_path, golden_dir, variant):
+    """The parity check above is not vacuous: against an oracle whose noise is missing, shared by the classes of a token
+    (it cancels in the softmax), added before the temperature division, or taken from the draw's own Philox block, the
+    same comparison at T = 0.7 exceeds the `bad <= 2` allowance by far (at least 1 % of the tokens: five times the
+    largest share any device parity test allows, 2e-3)."""
+    cfg = {"name": "gumbel", "temperature": 0.7}
+    bad = total = 0
+    for out, logp, i in _gumbel_case(harness, tmp_path, golden_dir, cfg):
+        bad += int((out != SC.wrong_gumbel_draw(logp, cfg, i, variant)).sum())
+        total += out.numel()
+    print(f"[host form vs WRONG oracle: {variant}] {bad}/{total}")
+    assert bad > 2 and bad >= 0.01 * total, f"{variant}: {bad}/{total}"
+
+
+def test_oracle_gumbel_noise_changes_the_draws(golden_dir):
+    """Oracle alone: on the same draw uniform, the tokens drawn with gumbel noise differ from the noise-free `random`
+    draws for a large share of the tokens — at least 5 %, ten times the widest device parity bound (5e-3) — so parity
+    on these inputs cannot be met by a sampler that drops or cancels the noise.  Counter word 1 matters too: the noise
+    of step i differs from that of step 0."""
+    spec, W = _weights("rico25")
+    g = np.load(os.path.join(golden_dir, "rico25_uncond_trajectory.npz"))
+    diff = total = 0
+    for i in GUMBEL_STATES:
+        toks = torch.from_numpy(g["states_before"][i].astype(np.int64))
+        logp = SC.oracle_logp(W, spec, toks, int(g["steps"][i]))
+        with_noise = SC.oracle_draw(logp, {"name": "gumbel", "temperature": 1.0}, i)
+        without = SC.oracle_draw(logp, {"name": "random", "temperature": 1.0}, i)
+        # without explicit noise a seeded gumbel draw keeps its earlier meaning (plain random): golden tests rely on it
+        B, S = toks.shape
+        u = R.token_uniforms(SC.SEED, SC.FIRST_LAYOUT, B, S, i)[..., 0]
+        assert torch.equal(R.sample_tokens(logp, {"name": "gumbel", "temperature": 1.0}, uniforms=u), without)
+        diff += int((with_noise != without).sum())
+        total += without.numel()
+    print(f"[oracle] gumbel vs noise-free draws on the same uniform: {diff}/{total} differ")
+    assert diff >= 0.05 * total, f"{diff}/{total}"
+    a = R.token_gumbel_uniforms(7, 3, 2, 5, 4, spec.n_class)
+    assert a.shape == (2, spec.n_class, 5) and a.dtype == np.float32 and (a > 0).all() and (a < 1).all()
+    assert not np.array_equal(a, R.token_gumbel_uniforms(7, 3, 2, 5, 0, spec.n_class))
+    # the noise words are disjoint from the draw's word (counter word 0 = pos, component 0)
+    d = R.token_uniforms(7, 3, 2, 5, 4, n=4)
+    assert not np.isin(a, d).any()
+
+
+# ----------------------------------------------------------------------------- parameter edges
+@pytest.mark.parametrize("ds", ["rico25", "publaynet"])
+def test_scalar_tail_parameter_edges(harness, tmp_path, golden_dir, ds):
+    """top_k = 1 / at, above every sub-vocabulary size / = C, top_p = 1 and below the largest probability, temperatures
+    0.05 .. the largest the live-class forms admit (SC.edge_cfgs) on states of the reference's trajectories (Rico25
+    unconditional; PubLayNet cond=c: strong mask + [PAD] disable), against R.single_step's draw on identical uniforms.
+    top_p = 1.0 is held to "nothing but rounding may be cut" (SC.top_p_one_mismatch).  Allowance: the file's rate of CDF-edge roundings (2 per 2 000 tokens) on the 4 000 tokens of each setting; never a
+    token outside the oracle's support; top_k = 1 is the argmax wherever the oracle's top-2 gap exceeds fp32 rounding."""
+    spec, W = _weights(ds)
+    states, cond = SC.load_states(golden_dir, ds)
+    cfgs = SC.edge_cfgs(spec)
+    bad = {k: 0 for k, _ in cfgs}
+    total = raw_top_p_one = 0
+    for i, t, toks in states:
+        _, logits, logp = R.single_step(W, spec, toks, t, {"name": "deterministic"}, cond, return_all=True)
+        top2 = logp.topk(2, dim=1).values
+        clear = (top2[:, 0] - top2[:, 1]) > 1e-4
+        total += toks.numel()
+        for name, cfg in cfgs:
+            out = _run(harness, tmp_path, spec, W, toks, t, logits, cfg, i, SC.SEED, SC.FIRST_LAYOUT, cond)
+            sup_cfg = {"name": "random", "temperature": 1.0} if name == "top_p1.0" else cfg   # (its cut is rounding: below)
+            assert SC.support(logp, sup_cfg).gather(1, out[:, None, :]).all(), (name, i)
+            if name == "top_p1.0":  # nothing but rounding may be cut: see SC.top_p_one_mismatch
+                raw_top_p_one += int((out != SC.oracle_draw(logp, cfg, i)).sum())
+                bad[name] += int(SC.top_p_one_mismatch(out, logp, cfg, i).sum())
+                continue
+            bad[name] += int((out != SC.oracle_draw(logp, cfg, i)).sum())
+            if name == "top_k1":
+                assert torch.equal(out[clear], logp.argmax(1)[clear]), i
+            if name == "top_p1e-3":  # only the first maximum survives: no randomness left
+                assert torch.equal(out[clear], logp.argmax(1)[clear]), i
+    print(f"[host form, {ds}] mismatches per setting over {total} tokens: {bad}; top_p = 1.0 against the oracle's own "
+          f"float32 cumsum: {raw_top_p_one}")
+    assert max(bad.values()) <= 2 * total // 2000, bad
+
+
+def test_live_class_form_needs_the_temperature_bound(harness, tmp_path, golden_dir):
+    """The live-class forms leave a token's dead classes (log(1e-30) each) out of the draw.  The reference divides by the
+    temperature first, so the dead classes hold C exp(log(1e-30) / T) of the mass: 2^-24 at SC.max_live_temperature(C)
+    (3.19 for the 155 classes of Rico25); at T = 10 the 121 dead classes of a bin token hold 121 * 1e-3 against a live mass of
+    at most 34 (34 live classes, each p^(1/10) <= 1), i.e. >= 0.35 % of the draws.  Inside the bound the live-class form (this host build
+    IS one: SlotMap<1, 64, LIVE>) draws the oracle's tokens; at T = 10 it cannot draw the dead classes the oracle draws —
+    which is why ldm_sample_step / ldm_sample_loop refuse such a temperature instead of approximating
+    (tests/test_sampler_edges_gpu.py::test_temperature_contract)."""
+    spec, W = _weights("rico25")
+    C = spec.n_class
+    assert 3.1 < SC.max_live_temperature(C) < 3.3
+    assert C * np.exp(SP.LOG_EPS / SC.admitted_temperature(C)) <= 2.0 ** -24 < C * np.exp(SP.LOG_EPS / (1.01 * SC.max_live_temperature(C)))
+    states, _ = SC.load_states(golden_dir, "rico25", steps=(3, 40, 80, 99))
+    dead_drawn = bad = total = 0
+    for i, t, toks in states:
+        _, logits, logp = R.single_step(W, spec, toks, t, {"name": "deterministic"}, return_all=True)
+        cfg = {"name": "random", "temperature": 10.0}
+        out = _run(harness, tmp_path, spec, W, toks, t, logits, cfg, i, SC.SEED, SC.FIRST_LAYOUT)
+        ref = SC.oracle_draw(logp, cfg, i)
+        dead_drawn += int((logp.gather(1, ref[:, None, :]) == logp.min()).sum())
+        bad += int((out != ref).sum())
+        total += ref.numel()
+    print(f"[host live-class form, T=10] oracle draws on dead classes {dead_drawn}/{total}; tokens differing {bad}/{total}")
+    assert dead_drawn >= 0.002 * total     # the reference's distribution does put >= 0.35 % of its mass there (docstring)
+    assert bad >= dead_drawn               # ... and the live-class form can follow none of those draws
