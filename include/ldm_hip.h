@@ -333,6 +333,26 @@ int ldm_relation_graph(const void* d_bbox, int box_f64, const int64_t* d_label, 
                        int64_t* d_first_node, void* d_node_box, int64_t* d_node_label, int64_t* d_node_batch,
                        uint8_t* d_canvas, int32_t* d_totals, int32_t* d_err, void* stream);
 
+/* ---- generated layouts as pictures (save_image of the sampling entry point) ---------------------------------------------
+ * trainer/helpers/visualization.py:17-115 (test.py:205-214): every layout on a white H x W canvas, its elements drawn from
+ * the larger to the smaller area (stable) as Pillow's ImageDraw.rectangle draws them — fill blended with alpha 100, opaque
+ * outline — pixel for pixel.  Device pointers in and out, no handle, the current device; box_f64 as above.
+ * d_bbox (B,S,4) xc yc w h, d_label (B,S) int64, d_mask (B,S) uint8 as ldm_decode_layouts leaves them; d_colors (n_colors,3)
+ * uint8 RGB per label.  1 <= S <= 256, 1 <= H, W <= 16384, 0 <= pad <= 16384, cols >= 1.
+ * d_out is a (GH, GW, 3) uint8 mosaic of B tiles in `cols` columns with `pad` black pixels around every tile, torchvision's
+ * make_grid(nrow, padding, pad_value = 0) for cols = min(nrow, B):
+ *   GH = ceil(B / cols) * (H + pad) + pad,  GW = cols * (W + pad) + pad   (ldm_render_grid_shape),
+ *   tile k starts at row (k / cols) * (H + pad) + pad, column (k % cols) * (W + pad) + pad.
+ * cols = 1, pad = 0 is the batch form (B, H, W, 3).  The padding and the empty tiles of a last row are zeroed by the call.
+ * *d_err (int32, zeroed by the call): bit 0 = an unmasked box is not finite or has a negative w or h (Pillow raises a
+ * ValueError), bit 1 = an unmasked label is outside [0, n_colors) (an IndexError); such an element is not drawn, every
+ * other one is.  Returns 0, -1 (bad argument: nothing launched) or -2 (launch failed). */
+int ldm_render_layouts(const void* d_bbox, int box_f64, const int64_t* d_label, const uint8_t* d_mask, int B, int S,
+                       const uint8_t* d_colors, int n_colors, int H, int W, int cols, int pad, uint8_t* d_out, int32_t* d_err,
+                       void* stream);
+/* (GH, GW) of the mosaic above; -1 when an argument is out of range.  Host only: no device is touched. */
+int ldm_render_grid_shape(int B, int H, int W, int cols, int pad, int64_t* GH, int64_t* GW);
+
 /* ---- introspection ------------------------------------------------------------------- */
 /* average device time (ms) of the most recent ldm_sample_loop, measured with HIP events on the
  * stream it ran on; blocks until that loop has finished. */

@@ -37,6 +37,8 @@ EXPORTS = (
     "ldm_relation_violation", "ldm_relation_violation_dense",
     # cond= inputs from raw layouts (bound in layout_dm_amd/task.py)
     "ldm_encode_cond", "ldm_relation_graph",
+    # generated layouts as pictures (bound in layout_dm_amd/visualization.py)
+    "ldm_render_layouts", "ldm_render_grid_shape",
 )
 
 
@@ -138,6 +140,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_relation_violation_dense.argtypes = [vp, i32, vp, i32, i32, vp] + graph
     lib.ldm_encode_cond.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]
     lib.ldm_relation_graph.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, C.c_double, u64, u64] + [vp] * 13
+    lib.ldm_render_layouts.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.ldm_render_grid_shape.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int

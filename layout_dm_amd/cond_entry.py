@@ -8,8 +8,11 @@ neither the reference, its datasets nor torch_geometric is needed, and the outpu
 
     LDM_COND_LAYOUTS=res/unconditional_.../seed_0.pkl python -m layout_dm_amd.cond_entry cond=refinement job_dir=JOB result_dir=res
 
-Everything else — `cond=unconditional`, the variable unset, the reference package importable — is `test_entry.main` unchanged
-(without the variable a conditional task stops with its SystemExit).
+With LDM_SAVE_VIS=1 the built-in runners also write the picture the reference saves of the first batch (test.py:205-214,
+layout_dm_amd/visualization.py) as <result_dir>/<cond>_<key>/test_generated.png; any other non-empty value is the path itself.
+
+Everything else — `cond=unconditional` without LDM_SAVE_VIS, both variables unset, the reference package importable — is
+`test_entry.main` unchanged (without LDM_COND_LAYOUTS a conditional task stops with its SystemExit).
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ from typing import Any, Dict, List, Optional
 
 from .test_entry import (SAMPLING_DEFAULTS, AttrDict, GeometryTokenizer, _filter_invalid, _find_ckpt_dirs, _plain, parse_cli)
 from .test_entry import main as _test_entry_main
+from .test_entry import run_builtin as _run_builtin
 
 COND_LAYOUTS_ENV = "LDM_COND_LAYOUTS"
 BUILTIN_COND_TYPES = ("c", "cwh", "partial", "refinement", "relation")
@@ -156,6 +160,12 @@ def run_builtin_conditional(test_cfg: AttrDict, layouts) -> Dict[str, Any]:
             t0 = time.time()
             out = model.sample(batch_size=batch_size, cond=cond, sampling_cfg=sampling_cfg, cond_type=test_cfg.cond)
             t_total += time.time() - t0
+            if n_total == 0:     # test.py:205-214, behind LDM_SAVE_VIS (off by default)
+                from . import visualization
+
+                vis = visualization.save_first_batch(out, result_dir, tokenizer.N_category)
+                if vis:
+                    summary.setdefault("images", []).append(vis)
             n_total += batch_size
             if cond["type"] in ("partial", "refinement"):   # test.py:216-227
                 ids = cond["seq_orig" if cond["type"] == "refinement" else "seq"]
@@ -188,6 +198,32 @@ def run_builtin_conditional(test_cfg: AttrDict, layouts) -> Dict[str, Any]:
     return summary
 
 
+def run_builtin_unconditional(test_cfg: AttrDict) -> Dict[str, Any]:
+    """test_entry.run_builtin, and with LDM_SAVE_VIS set the picture of batch 0 of every seed (test.py:205-214; each seed
+    overwrites the file, as the reference overwrites tmp/test_generated.png).  That runner keeps nothing but its pickle, so
+    batch 0 is read back from it: the first max_batch_size entries of `results`, one per layout with the invalid elements
+    already dropped in order — the elements, the order and so the pixels that drawing the batch under its mask gives."""
+    from . import task, visualization
+
+    summary = _run_builtin(test_cfg)
+    path = visualization.vis_path(summary["result_dir"])
+    if path is None:
+        return summary
+    for pkl in summary["pickles"]:
+        with open(pkl, "rb") as f:
+            first = pickle.load(f)["results"][:max(1, int(test_cfg.max_batch_size))]
+        if not first:
+            continue
+        import numpy as np
+        import torch
+
+        f64 = any(np.asarray(b).dtype == np.float64 for b, _ in first)
+        dense = task.layouts_from_list(first, max(1, max(len(l) for _, l in first)), torch.float64 if f64 else torch.float32)
+        n_colors = max(1, max((int(np.max(l)) + 1 for _, l in first if len(l)), default=1))   # (default_colors is prefix-stable)
+        summary.setdefault("images", []).append(visualization.save_first_batch(dense, summary["result_dir"], n_colors))
+    return summary
+
+
 def _reference_importable() -> bool:
     try:
         import hydra  # noqa: F401
@@ -204,6 +240,10 @@ def main(argv: Optional[List[str]] = None):
         cfg = parse_cli(argv)
         if cfg.cond != "unconditional":
             return run_builtin_conditional(cfg, load_cond_layouts(path))
+    if os.environ.get("LDM_SAVE_VIS") and not _reference_importable():
+        cfg = parse_cli(argv)
+        if cfg.cond == "unconditional":
+            return run_builtin_unconditional(cfg)
     return _test_entry_main(argv)
 
 

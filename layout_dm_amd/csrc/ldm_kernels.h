@@ -245,6 +245,12 @@ struct CondGraphArgs {
   int32_t* err;
 };
 void launch_relation_graph(const CondGraphArgs& a, hipStream_t st);
+// layouts -> uint8 RGB tiles of a (GH, GW, 3) mosaic (kernels_render.hip; tile origins: ldm_render::tile_origin); arguments
+// checked by the C-ABI (ldm_render_api.cpp), which also clears the mosaic's padding; *err bit 0 = a box that is not finite or
+// has a negative w / h, bit 1 = a label outside [0, n_colors)
+void launch_render_layouts(const void* bbox, int box_f64, const int64_t* label, const uint8_t* mask, int B, int S,
+                           const uint8_t* colors, int n_colors, int H, int W, int cols, int pad, int64_t GW, uint8_t* out,
+                           int32_t* err, hipStream_t st);
 // ids -> {bbox, label, mask} (kernels_decode.hip); centres: [4][n_bin] f64 cluster centres or nullptr (linear bins)
 void launch_decode_layouts(const int32_t* tokens, int B, int E, int A, int n_category, int n_bin,
                            const double* centres, int box_f64, void* bbox, int64_t* label, uint8_t* mask,
