@@ -183,8 +183,11 @@ extern "C" int ldm_fid_features(ldm_fid* h, const float* d_bbox, const int64_t* 
 }
 
 // ------------------------------------------------------------------------------------------ PRDC
-extern "C" int ldm_prdc(const float* d_real, int n_real, const float* d_fake, int n_fake, int dim, int nearest_k,
-                        float* h_out4, void* stream) {
+// The one launch sequence behind ldm_prdc and its stage hook.  The last four arguments are optional copies of the stages:
+// the squared radii (device), the raw counts {precision, recall, density, coverage} (host) and the real x fake squared-distance
+// matrix (device, n_real x n_fake).
+static int prdc_run(const float* d_real, int n_real, const float* d_fake, int n_fake, int dim, int nearest_k, float* h_out4,
+                    void* stream, float* d_r2_real, float* d_r2_fake, unsigned long long* h_counts4, float* d_drf) {
   if (!d_real || !d_fake || !h_out4 || n_real < 1 || n_fake < 1 || dim < 1) return -1;
   if (nearest_k < 1 || nearest_k > 7 || nearest_k + 1 > n_real || nearest_k + 1 > n_fake) return -1;
   hipStream_t st = (hipStream_t)stream;
@@ -214,13 +217,34 @@ extern "C" int ldm_prdc(const float* d_real, int n_real, const float* d_fake, in
   launch_prdc_counts(D, n_real, n_fake, r2r, r2f, cnt, st);
   unsigned long long h[4];
   if (hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) return done(-2);
+  if (d_r2_real && hipMemcpyAsync(d_r2_real, r2r, n_real * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return done(-2);
+  if (d_r2_fake && hipMemcpyAsync(d_r2_fake, r2f, n_fake * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return done(-2);
+  if (d_drf && hipMemcpyAsync(d_drf, D, (size_t)n_real * n_fake * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return done(-2);
   if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return done(-2);
+  if (h_counts4) memcpy(h_counts4, h, sizeof(h));
   // (the ratios in double like prdc, narrowed at the ABI)
   h_out4[0] = (float)((double)h[0] / (double)n_fake);                           // precision
   h_out4[1] = (float)((double)h[1] / (double)n_real);                           // recall
   h_out4[2] = (float)((double)h[2] / ((double)nearest_k * (double)n_fake));     // density
   h_out4[3] = (float)((double)h[3] / (double)n_real);                           // coverage
   return done(0);
+}
+
+extern "C" int ldm_prdc(const float* d_real, int n_real, const float* d_fake, int n_fake, int dim, int nearest_k,
+                        float* h_out4, void* stream) {
+  return prdc_run(d_real, n_real, d_fake, n_fake, dim, nearest_k, h_out4, stream, nullptr, nullptr, nullptr, nullptr);
+}
+
+// Development hook (NOT part of the public ABI in include/ldm_hip.h, like ldm_dev.cpp's): ldm_prdc's launch sequence, and besides the
+// four ratios its stages -- d_r2_real (n_real) / d_r2_fake (n_fake): the squared k-NN radii, float32 on the device; h_counts4: the raw
+// counts {precision, recall, density, coverage} on the host; d_drf (n_real x n_fake, may be NULL): the real x fake squared distances,
+// float32 on the device.  tests/test_prdc_exact_gpu.py.
+extern "C" int ldm_dev_prdc_stages(const float* d_real, int n_real, const float* d_fake, int n_fake, int dim, int nearest_k,
+                                   float* h_out4, float* d_r2_real, float* d_r2_fake, unsigned long long* h_counts4, float* d_drf,
+                                   void* stream) {
+  if (!d_r2_real || !d_r2_fake || !h_counts4) return -1;
+  return prdc_run(d_real, n_real, d_fake, n_fake, dim, nearest_k, h_out4, stream, d_r2_real, d_r2_fake, h_counts4, d_drf);
 }
 
 // ------------------------------------------------------------------------------------------ alignment / overlap
