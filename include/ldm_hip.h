@@ -333,6 +333,18 @@ int ldm_relation_graph(const void* d_bbox, int box_f64, const int64_t* d_label, 
                        int64_t* d_first_node, void* d_node_box, int64_t* d_node_label, int64_t* d_node_batch,
                        uint8_t* d_canvas, int32_t* d_totals, int32_t* d_err, void* stream);
 
+/* cond["weak_logits"] of cond=refinement (set_additional_conditions_for_refinement, helpers/task.py:154-224) from the tokens of
+ * cond["seq_orig"]:  d_out[b][c][s] = d_table[tok(b', s) * C + c] * weight, one float32 multiply (the sign of zero under a
+ * negative weight included), b' = b when B_seq == B and b' = 0 when B_seq == 1 (duplicate_cond: one conditioning layout, B
+ * samples).  d_seq_orig (B_seq,S) int64 (seq_i64 = 1, the reference's dtype) or int32 (0); d_table (C,C) float32 row-major
+ * [token][class], the table of _index_to_smoothed_log_onehot BEFORE refine_lambda; weight = refine_lambda (negated for
+ * refine_mode = negative); d_out (B,C,S) float32, what ldm_cond.d_weak_logits takes — any 4-byte aligned address.  S >= 1 and
+ * C >= 1 are otherwise free (the output is limited to 2^31 - 1 pieces of 16 KiB).  *d_err (int32, zeroed by the call): bit 0 = a
+ * token outside [0, C) (F.embedding raises an IndexError); its column of d_out is +0.0 and no table entry is read for it.
+ * B == 0: nothing is launched or touched, 0.  Returns 0, -1 (bad argument: nothing launched) or -2 (launch failed). */
+int ldm_refinement_prior(const void* d_seq_orig, int seq_i64, int B_seq, int B, int S, int C, const float* d_table, float weight,
+                         float* d_out, int32_t* d_err, void* stream);
+
 /* ---- generated layouts as pictures (save_image of the sampling entry point) ---------------------------------------------
  * trainer/helpers/visualization.py:17-115 (test.py:205-214): every layout on a white H x W canvas, its elements drawn from
  * the larger to the smaller area (stable) as Pillow's ImageDraw.rectangle draws them — fill blended with alpha 100, opaque

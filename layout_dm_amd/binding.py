@@ -37,6 +37,8 @@ EXPORTS = (
     "ldm_relation_violation", "ldm_relation_violation_dense",
     # cond= inputs from raw layouts (bound in layout_dm_amd/task.py)
     "ldm_encode_cond", "ldm_relation_graph",
+    # cond=refinement prior (refinement_prior below)
+    "ldm_refinement_prior",
     # generated layouts as pictures (bound in layout_dm_amd/visualization.py)
     "ldm_render_layouts", "ldm_render_grid_shape",
 )
@@ -140,6 +142,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_relation_violation_dense.argtypes = [vp, i32, vp, i32, i32, vp] + graph
     lib.ldm_encode_cond.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, vp]
     lib.ldm_relation_graph.argtypes = [vp, i32, vp, vp, i32, i32, i32, vp, C.c_double, u64, u64] + [vp] * 13
+    lib.ldm_refinement_prior.argtypes = [vp, i32, i32, i32, i32, i32, vp, C.c_float, vp, vp, vp]
     lib.ldm_render_layouts.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldm_render_grid_shape.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     for name in EXPORTS:
@@ -165,6 +168,45 @@ def make_sampler(cfg) -> LdmSampler:
 
 def _stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def refinement_prior(seq_orig: torch.Tensor, table_dev: torch.Tensor, weight: float, B: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cond["weak_logits"] of cond=refinement on the device (ldm_refinement_prior, kernels_refine.hip): the (B,C,S) float32
+    tensor `table_dev[seq_orig].permute(0, 2, 1) * weight`, bit for bit.  seq_orig: (B,S) or — one conditioning layout for B
+    samples — (1,S) ids, int64 or int32, on any device (a CPU tensor is uploaded: S ids per layout); table_dev: the (C,C)
+    float32 [token][class] table on the GPU, refine_lambda NOT applied.  Runs on the current stream of the table's device.
+    out: a contiguous (B,C,S) float32 tensor of that device to fill (any 4-byte aligned view), else one is allocated.
+    An id outside [0, C) raises IndexError like the indexing it replaces (this reads the error word: one synchronisation)."""
+    if not torch.cuda.is_available() or not table_dev.is_cuda:
+        raise RuntimeError("layout_dm_amd.binding.refinement_prior needs a ROCm GPU (MI355X); there is no CPU path")
+    lib = load_library()
+    dev = table_dev.device
+    if table_dev.dim() != 2 or table_dev.shape[0] != table_dev.shape[1] or table_dev.dtype != torch.float32:
+        raise ValueError(f"table_dev must be (C,C) float32; got {tuple(table_dev.shape)} {table_dev.dtype}")
+    seq = torch.as_tensor(seq_orig)
+    if seq.dim() != 2 or seq.shape[1] < 1 or seq.shape[0] not in (1, int(B)):
+        raise ValueError(f"seq_orig must be ({B},S) or (1,S), S >= 1; got {tuple(seq.shape)}")
+    if seq.dtype not in (torch.int32, torch.int64):
+        seq = seq.long()
+    seq = seq.to(dev).contiguous()
+    table = table_dev.contiguous()
+    C_, S = int(table.shape[0]), int(seq.shape[1])
+    if out is None:
+        out = torch.empty((int(B), C_, S), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (int(B), C_, S) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous ({B},{C_},{S}) float32 tensor on {dev}")
+    if int(B) == 0:
+        return out
+    err = torch.empty(1, dtype=torch.int32, device=dev)   # (zeroed by the call)
+    with torch.cuda.device(dev):
+        rc = lib.ldm_refinement_prior(seq.data_ptr(), int(seq.dtype == torch.int64), int(seq.shape[0]), int(B), S, C_,
+                                      table.data_ptr(), float(weight), out.data_ptr(), err.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        raise RuntimeError(f"ldm_refinement_prior failed ({rc})")
+    if int(err.item()) & 1:   # (synchronises: seq / table temporaries are done with)
+        raise IndexError(f"refinement prior: an id of seq_orig is outside [0, {C_})")
+    return out
 
 
 class Engine:

@@ -1,5 +1,5 @@
-// C-ABI of the cond= builder (include/ldm_hip.h, section "cond= inputs from raw layouts"): ldm_encode_cond and
-// ldm_relation_graph.  Handle-free like the metrics entry points: device pointers, sizes, a stream; every argument is checked
+// C-ABI of the cond= builder (include/ldm_hip.h, section "cond= inputs from raw layouts"): ldm_encode_cond,
+// ldm_relation_graph and ldm_refinement_prior.  Handle-free like the metrics entry points: device pointers, sizes, a stream; every argument is checked
 // before anything is launched.
 #include "../../include/ldm_hip.h"
 
@@ -11,6 +11,7 @@
 #include "ldm_kernels.h"
 
 #include "ldm_cond_core.h"
+#include "ldm_refine_core.h"
 
 using namespace ldm;
 
@@ -62,5 +63,18 @@ extern "C" int ldm_relation_graph(const void* d_bbox, int box_f64, const int64_t
                   d_edge_off, d_src, d_dst, d_attr, d_first_node, d_node_box, d_node_label, d_node_batch, d_canvas, d_totals,
                   d_err};
   launch_relation_graph(a, (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int ldm_refinement_prior(const void* d_seq_orig, int seq_i64, int B_seq, int B, int S, int C, const float* d_table,
+                                    float weight, float* d_out, int32_t* d_err, void* stream) {
+  if (!ldm_refine::args_ok(seq_i64, B_seq, B, S, C)) return -1;
+  if (B == 0) return 0;   // nothing to write, nothing launched
+  if (!d_seq_orig || !d_table || !d_out || !d_err) return -1;
+  if (!aligned(d_seq_orig, seq_i64 ? 8 : 4) || !aligned(d_table, 4) || ldm_refine::misalign_of(d_out) < 0) return -1;
+  if ((int64_t)B * ldm_refine::chunks_per_layout(S, C) > INT32_MAX) return -1;   // (one workgroup per 16 KiB of output)
+  (void)hipGetLastError();
+  if (hipMemsetAsync(d_err, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return -2;
+  launch_refinement_prior(d_seq_orig, seq_i64, B_seq, B, S, C, d_table, weight, d_out, d_err, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }

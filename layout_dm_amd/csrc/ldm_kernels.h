@@ -245,6 +245,10 @@ struct CondGraphArgs {
   int32_t* err;
 };
 void launch_relation_graph(const CondGraphArgs& a, hipStream_t st);
+// cond=refinement prior (kernels_refine.hip; arithmetic: ldm_refine_core.h): out (B,C,S) = table[seq[b or 0][s]][c] * weight; seq
+// (B_seq,S) int64 / int32, B_seq == B or 1; *err bit 0 = a token outside [0, C); arguments checked by the C-ABI (ldm_cond_api.cpp)
+void launch_refinement_prior(const void* seq, int seq_i64, int B_seq, int B, int S, int C, const float* table, float weight,
+                             float* out, int32_t* err, hipStream_t st);
 // layouts -> uint8 RGB tiles of a (GH, GW, 3) mosaic (kernels_render.hip; tile origins: ldm_render::tile_origin); arguments
 // checked by the C-ABI (ldm_render_api.cpp), which also clears the mosaic's padding; *err bit 0 = a box that is not finite or
 // has a negative w / h, bit 1 = a label outside [0, n_colors)

@@ -84,13 +84,17 @@ def refinement_prior_table(tokenizer, mode: str, ratio: float) -> torch.Tensor:
     return table.float()
 
 
-def refinement_weak_logits(tokenizer, seq_orig: torch.Tensor, sampling_cfg, cache: Optional[dict] = None):
-    """cond["weak_logits"] of set_additional_conditions_for_refinement (helpers/task.py:204-224): (B,C,S)."""
+def _refine_settings(sampling_cfg):
+    """(mode, ratio, signed weight): refine_lambda, negated for refine_mode="negative" (helpers/task.py:210-214)."""
     mode = _cfg_get(sampling_cfg, "refine_mode", "uniform")
     ratio = float(_cfg_get(sampling_cfg, "refine_offset_ratio", 0.1))
     w = float(_cfg_get(sampling_cfg, "refine_lambda", 3.0))
     if mode == "negative":
         w *= -1.0
+    return mode, ratio, w
+
+
+def _cached_prior_table(tokenizer, mode: str, ratio: float, cache: Optional[dict]) -> torch.Tensor:
     key = (mode, ratio)
     if cache is None or cache.get("key") != key:
         table = refinement_prior_table(tokenizer, mode, ratio)
@@ -98,7 +102,40 @@ def refinement_weak_logits(tokenizer, seq_orig: torch.Tensor, sampling_cfg, cach
             cache["key"], cache["table"] = key, table
     else:
         table = cache["table"]
+    return table
+
+
+def refinement_weak_logits(tokenizer, seq_orig: torch.Tensor, sampling_cfg, cache: Optional[dict] = None):
+    """cond["weak_logits"] of set_additional_conditions_for_refinement (helpers/task.py:204-224): (B,C,S), on the host."""
+    mode, ratio, w = _refine_settings(sampling_cfg)
+    table = _cached_prior_table(tokenizer, mode, ratio, cache)
     return (table[seq_orig.cpu().long()].permute(0, 2, 1) * w).contiguous()
+
+
+def refinement_weak_logits_device(tokenizer, seq_orig: torch.Tensor, sampling_cfg, batch_size: int,
+                                  cache: Optional[dict] = None, device=None) -> torch.Tensor:
+    """The same tensor built on the GPU (binding.refinement_prior, kernels_refine.hip), bit for bit: (batch_size,C,S) float32
+    on the device.  seq_orig is taken from wherever it lives — a CPU tensor costs the upload of its ids (250 KB at B = 512
+    instead of the 40 MB prior), a device tensor no host transfer at all — as (batch_size,S) or, one conditioning layout
+    for batch_size samples (duplicate_cond), (1,S).  The (C,C) table of refinement_prior_table is built once on the host
+    and its device copy kept in `cache` per (mode, ratio, device); refine_lambda goes to the kernel as its weight.
+    device: where to build it (default: seq_orig's GPU, else the current one).  No CPU path."""
+    from . import binding
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("layout_dm_amd.layoutdm.refinement_weak_logits_device needs a ROCm GPU (MI355X); there is no CPU path")
+    mode, ratio, w = _refine_settings(sampling_cfg)
+    seq_orig = torch.as_tensor(seq_orig)
+    if device is None:
+        device = seq_orig.device if seq_orig.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    key = ("device", mode, ratio, str(device))
+    table_dev = cache.get(key) if cache is not None else None
+    if table_dev is None:
+        table_dev = _cached_prior_table(tokenizer, mode, ratio, cache).to(device).contiguous()
+        if cache is not None:
+            cache[key] = table_dev
+    return binding.refinement_prior(seq_orig, table_dev, w, int(batch_size))
 
 
 def device_decode_plan(tokenizer):
@@ -226,7 +263,18 @@ class LayoutDM:
             if ctype == "refinement" and "weak_logits" not in cond:
                 # set_additional_conditions_for_refinement (helpers/task.py:204-224) runs on the cond as given —
                 # (1,S) for a single conditioning layout — and duplicate_cond repeats the result once, in sample()
-                cond["weak_logits"] = self._weak_logits(cond["seq_orig"], sampling_cfg)
+                # — here as the kernel's broadcast form: (1,S) ids -> (batch_size,C,S), built on the device (kernels_refine.hip)
+                if self._refine_table is None:
+                    self._refine_table = {}
+                seq_orig = torch.as_tensor(cond["seq_orig"])
+                if inner.engine.device.type == "cuda":
+                    cond["weak_logits"] = refinement_weak_logits_device(
+                        self.tokenizer, seq_orig, sampling_cfg, int(batch_size) if seq_orig.size(0) == 1 else seq_orig.size(0),
+                        self._refine_table, device=inner.engine.device)
+                else:
+                    # the prior lives where the engine does.  binding.Engine exists on a GPU only (it raises without one), so this
+                    # is a stand-in engine on the host: tests/test_entry_reference_main.py drives the plumbing above the C-ABI so
+                    cond["weak_logits"] = self._weak_logits(seq_orig, sampling_cfg)
             if ctype == "relation":
                 from .relation import sample_with_relation
 
