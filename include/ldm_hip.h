@@ -17,6 +17,7 @@
 #ifndef LDM_HIP_H
 #define LDM_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -344,6 +345,61 @@ int ldm_relation_graph(const void* d_bbox, int box_f64, const int64_t* d_label, 
  * B == 0: nothing is launched or touched, 0.  Returns 0, -1 (bad argument: nothing launched) or -2 (launch failed). */
 int ldm_refinement_prior(const void* d_seq_orig, int seq_i64, int B_seq, int B, int S, int C, const float* d_table, float weight,
                          float* d_out, int32_t* d_err, void* stream);
+
+/* ---- coordinate bins from raw boxes (bin/clustering_coordinates.py) -------------------------------------------------------
+ * The cluster centres the kmeans / percentile tokenizers read, fitted one coordinate at a time: sklearn KMeans(n_init
+ * restarts of greedy k-means++ + Lloyd, the lowest inertia wins) and the reference's Percentile.fit.  Device pointers, no
+ * handle, the current device.  The rules and every summation order: layout_dm_amd/csrc/ldm_cluster_core.h; all sums are
+ * float64 in a fixed order and no floating-point atomic is used, so two runs give the same bits.  Own draws are Philox4x32-10
+ * keyed by (random_state, problem id, restart): sklearn's distribution, not its stream.
+ * A arrays of n float32 values each, row-major (A, n), 1 <= n <= 2^30; cluster counts 1 <= k <= 256, k <= n.
+ * d_work: a 256-byte aligned workspace of at least ldm_cluster_workspace_bytes(A, n, P, n_init) bytes (P problems of n_init
+ * restarts each; P = 0 measures ldm_cluster_sort alone).  One size serves every call below with those A, n, P, n_init.
+ * Problems are rows {array, k, problem id} of an int32 (P, 3) table with k non-increasing, given twice: h_prob on the host
+ * (launch shapes, checks) and d_prob, the same rows on the device.  Centres come back as (P, 256) rows, sorted, k valid.
+ * Every call returns 0, -1 (bad argument: nothing launched) or -2 (launch failed). */
+int ldm_cluster_workspace_bytes(int A, int64_t n, int P, int n_init, size_t* bytes);
+/* Sorts each array ascending (clip01 = 1: clipped to [0, 1] first, what Percentile.fit does) and derives what the fits read:
+ * d_sorted (A, n); d_ps / d_ps2 (A, n + 1) float64 prefix sums of x and x^2, [0] = 0; d_unique (A, n) the distinct values in
+ * front and zeros behind; d_ps_unique (A, n + 1) their prefix sums; d_n_unique (A) int64.  *d_err (int32, zeroed by the call):
+ * bit 0 = a NaN or an infinity in the input.  stages: LDM_CLUSTER_STAGE_SORT | LDM_CLUSTER_STAGE_DERIVE for the whole of
+ * it; one of the two runs that half alone (for timing them apart; the error word belongs to the sort half). */
+#define LDM_CLUSTER_STAGE_SORT 1   /* d_x -> d_sorted */
+#define LDM_CLUSTER_STAGE_DERIVE 2 /* d_sorted -> prefix sums, distinct values (d_sorted as an earlier call left it) */
+int ldm_cluster_sort(const float* d_x, int A, int64_t n, int clip01, int stages, float* d_sorted, double* d_ps, double* d_ps2, float* d_unique,
+                     double* d_ps_unique, int64_t* d_n_unique, void* d_work, size_t work_bytes, int32_t* d_err, void* stream);
+/* P problems x n_init restarts (1 <= n_init <= 64, P * n_init <= 65535) in one batch: seeding, Lloyd until sklearn's stopping
+ * rule (tol * var(X), no boundary moved, max_iter), inertia by a direct pass; per problem the restart of the lowest inertia,
+ * the lowest restart index on a tie.  first_restart: the restart index of the first of the n_init (a fit cut into several
+ * calls draws the same numbers).  An empty cluster keeps its centre.  The caller makes sure every array holds at least k
+ * distinct values (d_n_unique).  d_centres (P, 256) float64, d_inertia (P) float64, d_n_iter / d_best_restart (P) int32. */
+int ldm_kmeans1d_fit(const float* d_sorted, const double* d_ps, const double* d_ps2, int A, int64_t n, const int32_t* h_prob,
+                     const int32_t* d_prob, int P, int n_init, int first_restart, uint64_t random_state, int max_iter, double tol,
+                     double* d_centres, double* d_inertia, int32_t* d_n_iter, int32_t* d_best_restart, void* d_work,
+                     size_t work_bytes, void* stream);
+/* Lloyd alone from explicit start centres d_start (P, 256) float64, each row's first k sorted ascending: the parity hook
+ * against sklearn KMeans(init=..., n_init=1).  d_trace (max_iter, k) float64 or NULL: the centres after every iteration run
+ * (P == 1 only). */
+int ldm_kmeans1d_lloyd(const float* d_sorted, const double* d_ps, const double* d_ps2, int A, int64_t n, const int32_t* h_prob,
+                       const int32_t* d_prob, int P, const double* d_start, int max_iter, double tol, double* d_centres,
+                       double* d_inertia, int32_t* d_n_iter, double* d_trace, void* d_work, size_t work_bytes, void* stream);
+/* Percentile.fit on the distinct values ldm_cluster_sort(clip01 = 1) left: h_n_unique (A) int64 on the host (the k rank
+ * thresholds int(t_i * m) are evaluated there, in float64); d_centres (P, 256) float32, -1.0f for an empty bin.  Waits for
+ * the stream. */
+int ldm_percentile_fit(const double* d_ps_unique, int A, int64_t n, const int64_t* h_n_unique, const int32_t* h_prob,
+                       const int32_t* d_prob, int P, float* d_centres, void* d_work, size_t work_bytes, void* stream);
+/* predict: d_ids[i] = the bin ldm_encode_cond gives value d_x[i] under d_centres (k) float64 sorted centres; quant =
+ * LDM_QUANT_KMEANS or LDM_QUANT_PERCENTILE.  The same routine, not a second rule. */
+int ldm_nearest_centre(const float* d_x, int64_t n, const double* d_centres, int k, int quant, int32_t* d_ids, void* stream);
+/* Development hook: one run (one array, one k, one restart) with every stage kept.  d_sorted (n), d_ps / d_ps2 (n + 1); per
+ * seeding step s < k, 7 slots each of which the first L are written (L = 1 at s = 0, else 2 + int(ln k)): d_unif the uniforms,
+ * d_cand (int64) the candidate indices into d_sorted, d_pots the potential each would leave; d_pick (k) int64 the index kept;
+ * d_dist (k, n) float64 or NULL: the squared distances the draws of step s >= 1 were made over (row 0 is not written);
+ * d_lloyd (max_iter, k) the centres after each iteration run; d_centres (256), d_inertia (1), d_n_iter (1). */
+int ldm_dev_cluster_stages(const float* d_x, int64_t n, int k, uint64_t random_state, int problem_id, int restart, int max_iter,
+                           double tol, float* d_sorted, double* d_ps, double* d_ps2, double* d_unif, int64_t* d_cand,
+                           double* d_pots, int64_t* d_pick, double* d_dist, double* d_lloyd, double* d_centres, double* d_inertia,
+                           int32_t* d_n_iter, void* d_work, size_t work_bytes, int32_t* d_err, void* stream);
 
 /* ---- generated layouts as pictures (save_image of the sampling entry point) ---------------------------------------------
  * trainer/helpers/visualization.py:17-115 (test.py:205-214): every layout on a white H x W canvas, its elements drawn from

@@ -41,6 +41,9 @@ EXPORTS = (
     "ldm_refinement_prior",
     # generated layouts as pictures (bound in layout_dm_amd/visualization.py)
     "ldm_render_layouts", "ldm_render_grid_shape",
+    # coordinate bins from raw boxes (bound in layout_dm_amd/clustering.py)
+    "ldm_cluster_workspace_bytes", "ldm_cluster_sort", "ldm_kmeans1d_fit", "ldm_kmeans1d_lloyd", "ldm_percentile_fit",
+    "ldm_nearest_centre", "ldm_dev_cluster_stages",
 )
 
 
@@ -145,6 +148,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_refinement_prior.argtypes = [vp, i32, i32, i32, i32, i32, vp, C.c_float, vp, vp, vp]
     lib.ldm_render_layouts.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.ldm_render_grid_shape.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    i64, sz, f64 = C.c_int64, C.c_size_t, C.c_double
+    lib.ldm_cluster_workspace_bytes.argtypes = [i32, i64, i32, i32, C.POINTER(sz)]
+    lib.ldm_cluster_sort.argtypes = [vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.ldm_kmeans1d_fit.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32, i32, i32, u64, i32, f64, vp, vp, vp, vp, vp, sz, vp]
+    lib.ldm_kmeans1d_lloyd.argtypes = [vp, vp, vp, i32, i64, vp, vp, i32, vp, i32, f64, vp, vp, vp, vp, vp, sz, vp]
+    lib.ldm_percentile_fit.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, sz, vp]
+    lib.ldm_nearest_centre.argtypes = [vp, i64, vp, i32, i32, vp, vp]
+    lib.ldm_dev_cluster_stages.argtypes = [vp, i64, i32, u64, i32, i32, i32, f64] + [vp] * 13 + [sz, vp, vp]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int

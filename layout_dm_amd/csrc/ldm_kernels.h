@@ -249,6 +249,57 @@ void launch_relation_graph(const CondGraphArgs& a, hipStream_t st);
 // (B_seq,S) int64 / int32, B_seq == B or 1; *err bit 0 = a token outside [0, C); arguments checked by the C-ABI (ldm_cond_api.cpp)
 void launch_refinement_prior(const void* seq, int seq_i64, int B_seq, int B, int S, int C, const float* table, float weight,
                              float* out, int32_t* err, hipStream_t st);
+// coordinate bins (kernels_cluster.hip; arithmetic and summation orders: ldm_cluster_core.h); arguments checked and the
+// workspace carved by the C-ABI (ldm_cluster_api.cpp)
+struct ClusterSortArgs {
+  const float* x;              // (A, n)
+  int A;
+  int64_t n;
+  int clip;                    // clip to [0, 1] first (percentile)
+  float* sorted;               // (A, n)
+  double *ps, *ps2;            // (A, n + 1) prefix sums of x and x^2 over `sorted`
+  float* unique;               // (A, n): the distinct values in front, zeros behind
+  double* ps_unique;           // (A, n + 1)
+  int64_t* n_unique;           // (A)
+  int32_t* err;                // bit 0: a NaN or an infinity
+  uint32_t *keys_a, *keys_b;   // workspace (A, n) each
+  uint32_t* hist;              // workspace (A, 256, tiles of kSortTile)
+  double *tile_tot, *tile_front;   // workspace (A, tiles of kScanTile, 2) each
+  double* rank;                // workspace (A, n + 1)
+};
+void launch_cluster_sort(const ClusterSortArgs& s, int stages, hipStream_t st);   // stages: 1 = sort, 2 = everything derived from `sorted`
+struct ClusterFitArgs {
+  const float* sorted;         // (A, n)
+  const double *ps, *ps2;      // (A, n + 1)
+  int64_t n, tiles;            // tiles of kSeedTile points
+  int P, n_init, Q;            // problems, restarts each, Q = P * n_init runs; run q = problem q / n_init, restart q % n_init
+  int first_restart;           // restart index of a problem's first run (the Philox counter word; a fit may be cut into calls)
+  const int32_t* prob;         // device (P, 3): {array, k, problem id}
+  uint64_t random_state;
+  int max_iter;
+  double tol;
+  double* cs;                  // (Q, kMaxK) sorted centres of every run: the start centres in, the fitted ones out
+  double* wc;                  // (2, Q, kMaxCand, tiles) per-tile potentials of the candidates, double-buffered over steps
+  int64_t* cand;               // (Q, kMaxCand)
+  double* pot;                 // (Q)
+  int32_t* best;               // (Q)
+  int32_t* n_iter_q;           // (Q)
+  double* centres;             // out (P, kMaxK)
+  double* inertia;             // out (P)
+  int32_t *n_iter, *best_restart;   // out (P)
+  // development traces of a single run (Q == 1), or nullptr
+  double* t_unif;              // (k, kMaxCand)
+  int64_t* t_cand;             // (k, kMaxCand)
+  double* t_pots;              // (k, kMaxCand)
+  int64_t* t_pick;             // (k)
+  double* t_dist;              // (k, n) squared distances the draws of a step were made over (step 0: untouched), or nullptr
+  double* t_lloyd;             // (max_iter, k)
+};
+// h_k: host copy of the problems' k (non-increasing); seed = 0: cs holds explicit start centres
+void launch_cluster_fit(const ClusterFitArgs& a, const int32_t* h_k, int seed, hipStream_t st);
+void launch_percentile(const double* ps_unique, int64_t n, const int32_t* prob, const int64_t* idx, int P, float* centres,
+                       hipStream_t st);
+void launch_nearest_centre(const float* x, int64_t n, const double* centres, int k, int quant, int32_t* ids, hipStream_t st);
 // layouts -> uint8 RGB tiles of a (GH, GW, 3) mosaic (kernels_render.hip; tile origins: ldm_render::tile_origin); arguments
 // checked by the C-ABI (ldm_render_api.cpp), which also clears the mosaic's padding; *err bit 0 = a box that is not finite or
 // has a negative w / h, bit 1 = a label outside [0, n_colors)

@@ -315,3 +315,17 @@ def synth_fid_state_dict(num_label: int, seed: int = 0, max_bbox: int = 25):
         sd[p + "norm1.weight"], sd[p + "norm1.bias"] = g(D), b(D)
         sd[p + "norm2.weight"], sd[p + "norm2.bias"] = g(D), b(D)
     return sd
+
+
+def synth_boxes(n: int, seed: int = 0, width: int = 1440, height: int = 2560) -> np.ndarray:
+    """(n, 4) float32 xc, yc, w, h of layout-like boxes: pixel-aligned on a width x height canvas (so coordinates repeat, as a
+    dataset's do), narrow heights, a share of full-width elements — the input of the coordinate-bin fits when no dataset is at
+    hand (tools/clustering_bench.py)."""
+    g = np.random.default_rng(seed)
+    w = np.clip(np.round(g.beta(1.2, 2.5, n) * width), 1, width)
+    h = np.clip(np.round(g.beta(1.0, 6.0, n) * height), 1, height)
+    full = g.random(n) < 0.15
+    w[full] = width
+    x0 = np.round(g.random(n) * (width - w))
+    y0 = np.round(g.random(n) * (height - h))
+    return np.stack([(x0 + w / 2) / width, (y0 + h / 2) / height, w / width, h / height], axis=1).astype(np.float32)

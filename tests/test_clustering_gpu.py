@@ -1,0 +1,353 @@
+"""Coordinate bins from raw boxes on the device (layout_dm_amd/clustering.py, kernels_cluster.hip).
+
+Sort and prefix sums through the stage hook against numpy (and the host build, bit for bit); explicit-start Lloyd against the
+scikit-learn fixture and the host build's per-iteration centres, bit for bit; every seeding step of the hook re-derived from
+its own uniforms and distances (the host core's inverse-CDF pick, numpy potentials, the argmin) and a chi-square test of the
+second centre on six points; full fits against the fixture's sklearn inertias, its dynamic-programming optimum and the
+fixed-point property; the percentile fit against the reference's centres; fit_coordinate_bins, the pickle round trip through
+GeometryTokenizer, task.encode and the device decode, the entry point; the refusals."""
+import math
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+import _clustering_cases as CC
+from _sampler_cases import chi_square
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def cuda():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a ROCm device (no CPU fallback exists)")
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def host_exe(tmp_path_factory):
+    return CC.build_host(tmp_path_factory.mktemp("cluster_gpu"))
+
+
+@pytest.fixture(scope="module")
+def cl(cuda):
+    from layout_dm_amd import clustering
+
+    return clustering
+
+
+def bits32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def bits64(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+# ----------------------------------------------------------------------------------------------------------------- sort
+def _sort_inputs(n, g):
+    x = ((g.random(n) - 0.3) * 2).astype(np.float32)
+    yield "random", x
+    yield "boxes", g.random(n).astype(np.float32)          # non-negative, like coordinates: the literal prefix-sum bound
+    yield "equal", np.full(n, 0.375, np.float32)
+    if n <= 70001:
+        yield "sorted", np.sort(x)
+        yield "reversed", np.sort(x)[::-1].copy()
+        yield "two values", np.where(g.random(n) < 0.5, np.float32(0.25), np.float32(-0.5)).astype(np.float32)
+        z = np.where(g.random(n) < 0.5, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
+        z[::3] = g.choice(np.array([1e-3, -1e-3], np.float32), len(z[::3]))
+        yield "signed zeros", z
+        d = (g.integers(-(2 ** 23) + 1, 2 ** 23, n).astype(np.float64) * 2.0 ** -149).astype(np.float32)   # denormals of both signs
+        d[::5] = g.random(len(d[::5])).astype(np.float32) * np.float32(1e-30)
+        yield "denormals", d
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 1023, 4097, 70001, 1000003])
+def test_sort_and_prefix_sums(cl, host_exe, tmp_path, n):
+    g = np.random.default_rng(n)
+    for name, x in _sort_inputs(n, g):
+        st = cl.cluster_stages(x, 1, max_iter=1)
+        want = np.sort(x)
+        assert np.array_equal(st["sorted"], want), (n, name)                       # values compare ==
+        assert np.array_equal(np.sort(bits32(st["sorted"])), np.sort(bits32(x))), (n, name)   # the same multiset of bit patterns
+        v = st["sorted"].astype(np.float64)
+        # <= n 2^-52 relative to np.cumsum itself wherever the data are non-negative (coordinates are).  With both signs the
+        # running sum passes through zero and no summation order can meet a bound relative to it: there the bound is relative to
+        # the running sum of magnitudes, which is what (n - 1) roundings of 2^-53 in either order amount to
+        mag = np.abs(np.cumsum(v)) if (v >= 0).all() else np.cumsum(np.abs(v))
+        for got, ref, m in ((st["ps"], np.cumsum(v), mag), (st["ps2"], np.cumsum(v * v), np.cumsum(v * v))):
+            assert got[0] == 0.0 and (np.abs(got[1:] - ref) <= n * 2.0 ** -52 * m).all(), (n, name)
+        again = cl.cluster_stages(x, 1, max_iter=1)
+        for key in ("sorted", "ps", "ps2", "centres", "inertia"):
+            assert st[key].tobytes() == again[key].tobytes(), (n, name, key)     # two runs: identical bits
+        if name in ("random", "boxes"):
+            if n <= 70001:
+                ps, ps2 = CC.host_prefix(host_exe, tmp_path, st["sorted"])
+                assert np.array_equal(bits64(ps), bits64(st["ps"])) and np.array_equal(bits64(ps2), bits64(st["ps2"])), n
+            assert st["n_iter"][0] == 1 and st["centres"][0] == st["ps"][n] / n
+
+
+# ---------------------------------------------------------------------------------------------------------------- Lloyd
+@pytest.mark.parametrize("n,k", CC.LLOYD_NK)
+def test_lloyd_against_sklearn_and_the_host_build(cl, host_exe, tmp_path, n, k):
+    g = CC.golden()
+    x, c0 = g[f"lloyd_{n}_{k}_x"], g[f"lloyd_{n}_{k}_c0"]
+    for M in CC.LLOYD_M:
+        km = cl.KMeans1D(k, max_iter=M, tol=0.0).fit(x.astype(np.float64).reshape(-1, 1), init=c0)
+        assert km.cluster_centers_.shape == (k, 1) and km.cluster_centers_.dtype == np.float64
+        CC.check_lloyd(km.cluster_centers_[:, 0], km.inertia_, km.n_iter_, g, n, k, M)
+    # the centres after every iteration: device == host build, bit for bit
+    s = cl._Sorted(torch.from_numpy(x.copy()).cuda()[None].contiguous(), False, 1, 1, "test")
+    cen, ine, nit, trace = cl._lloyd_batch(s, [(0, k)], [c0], 300, 0.0, trace=True)
+    host = CC.host_lloyd(host_exe, tmp_path, x, c0, 300, 0.0)
+    assert int(nit[0]) == host["n_iter"] and np.array_equal(bits64(trace[:host["n_iter"]]), bits64(host["trace"]))
+    assert np.array_equal(bits64(cen[0, :k]), bits64(host["centres"])) and np.isnan(trace[host["n_iter"]:]).all()
+    assert abs(float(ine[0]) - host["inertia"]) <= 1e-12 * host["inertia"]
+    # several problems in one call: each equal to its own call
+    both = cl._lloyd_batch(s, [(0, 3), (0, k)], [c0[:3], c0], 300, 0.0)
+    assert np.array_equal(bits64(both[0][1, :k]), bits64(cen[0, :k])) and both[2][1] == nit[0]
+
+
+# -------------------------------------------------------------------------------------------------------------- seeding
+@pytest.mark.parametrize("data,k,state", [("cont", 32, 0), ("grid", 128, 7), ("mix", 4, 2 ** 40 + 3)])
+def test_seeding_steps_rederived_from_the_hook(cl, host_exe, tmp_path, data, k, state):
+    x = CC.golden()[f"full_{data}_x"]
+    n = len(x)
+    st = cl.cluster_stages(x, k, random_state=state, restart=3, want_dist=True)
+    xs = st["sorted"].astype(np.float64)
+    L = 2 + int(math.log(k))
+    rows = [(k, 3, s, c) for s in range(k) for c in range(7)]
+    unif = CC.host_philox(host_exe, tmp_path, state, rows).reshape(k, 7)
+    chosen = []
+    for s in range(k):
+        nc = 1 if s == 0 else L
+        u, cand, pots, pick = st["unif"][s], st["cand"][s], st["pots"][s], int(st["pick"][s])
+        assert np.array_equal(u[:nc], unif[s, :nc]) and np.isnan(u[nc:]).all() and (cand[nc:] == -1).all()
+        assert ((cand[:nc] >= 0) & (cand[:nc] < n)).all() and pick in cand[:nc].tolist()      # a data point, among the candidates
+        if s == 0:
+            assert cand[0] == int(u[0] * n)
+            d = np.full(n, np.inf)
+        else:
+            d = ((xs[:, None] - np.asarray(chosen)[None, :]) ** 2).min(axis=1)
+            assert np.array_equal(st["dist"][s], d), s                                        # exact differences, one rounding each
+            assert np.array_equal(CC.host_pick(host_exe, tmp_path, st["dist"][s], u[:nc]), cand[:nc]), s
+            assert (d[cand[:nc]] > 0).all()                                                   # never a point of zero weight
+        want = np.array([np.minimum(d, (xs - xs[c]) ** 2).sum() for c in cand[:nc]])
+        assert (np.abs(pots[:nc] - want) <= 1e-12 * want).all(), (s, pots[:nc], want)
+        best = int(np.argmin(want))
+        if pick != cand[best]:
+            l = cand[:nc].tolist().index(pick)
+            assert abs(want[l] - want[best]) <= 1e-12 * want[best], (s, want)
+        chosen.append(xs[pick])
+    # Lloyd starts from the sorted picks and follows the host build bit for bit, the tolerance stop included
+    host = CC.host_lloyd(host_exe, tmp_path, x, np.sort(chosen), 300, 1e-4)
+    assert host["rc"] == 0 and int(st["n_iter"][0]) == host["n_iter"] < 300
+    assert np.array_equal(bits64(st["lloyd"]), bits64(host["trace"])) and np.array_equal(bits64(st["centres"]), bits64(host["centres"]))
+
+
+def test_second_centre_follows_the_greedy_d2_distribution(cl, cuda):
+    """n = 6, k = 2, 4000 restarts: the first centre is uniform; two candidates are drawn iid by D^2 and the one leaving the
+    smaller potential is kept (the first drawn on a tie).  Chi-square of the second centre's frequencies against the exact
+    probabilities, at the bound the sampler tests use (_sampler_cases.chi_square: dof + 6 sqrt(2 dof) + 10)."""
+    import ctypes as C
+
+    from layout_dm_amd.binding import _stream_ptr, load_library
+
+    x = np.array([0.0, 0.1, 0.15, 0.4, 0.7, 1.0], np.float32)
+    v = x.astype(np.float64)
+    n, k, R = 6, 2, 4000
+    phi = np.array([[np.minimum((v - v[i]) ** 2, (v - v[j]) ** 2).sum() for j in range(n)] for i in range(n)])
+    p2 = np.zeros(n)
+    for i in range(n):
+        p = (v - v[i]) ** 2
+        p /= p.sum()
+        for a in range(n):
+            for b in range(n):
+                p2[a if phi[i, a] <= phi[i, b] else b] += p[a] * p[b] / n
+    assert abs(p2.sum() - 1) < 1e-12
+    lib = load_library()
+    need = C.c_size_t()
+    assert lib.ldm_cluster_workspace_bytes(1, n, 1, 1, C.byref(need)) == 0
+    f64 = dict(dtype=torch.float64, device=cuda)
+    dx = torch.from_numpy(x).to(cuda)
+    work = torch.empty(need.value, dtype=torch.uint8, device=cuda)
+    srt, ps, ps2 = torch.empty(n, dtype=torch.float32, device=cuda), torch.empty(n + 1, **f64), torch.empty(n + 1, **f64)
+    unif, pots, lloyd, cen, ine = (torch.empty(s, **f64) for s in ((k, 7), (k, 7), (1, k), (256,), (1,)))
+    cand = torch.empty((k, 7), dtype=torch.int64, device=cuda)
+    picks = torch.empty((R, k), dtype=torch.int64, device=cuda)
+    nit, err = torch.empty(1, dtype=torch.int32, device=cuda), torch.empty(1, dtype=torch.int32, device=cuda)
+    for r in range(R):
+        rc = lib.ldm_dev_cluster_stages(dx.data_ptr(), n, k, 11, k, r, 1, 0.0, srt.data_ptr(), ps.data_ptr(), ps2.data_ptr(),
+                                        unif.data_ptr(), cand.data_ptr(), pots.data_ptr(), picks[r].data_ptr(), None, lloyd.data_ptr(),
+                                        cen.data_ptr(), ine.data_ptr(), nit.data_ptr(), work.data_ptr(), work.numel(), err.data_ptr(),
+                                        _stream_ptr(cuda))
+        assert rc == 0
+    picks = picks.cpu().numpy()
+    assert (picks[:, 0] != picks[:, 1]).all()
+    chi2, dof, bound, _, _ = chi_square(picks[:, 0], np.full(n, 1 / n), n)
+    print(f"first centre: chi2 {chi2:.2f} (dof {dof}, bound {bound:.1f})")
+    assert dof == 5 and chi2 <= bound
+    chi2, dof, bound, other, n_other = chi_square(picks[:, 1], p2, n)
+    print(f"second centre: chi2 {chi2:.2f} (dof {dof}, bound {bound:.1f}), p = {np.round(p2, 4)}")
+    assert n_other == 0 and dof == 5 and chi2 <= bound
+
+
+# ------------------------------------------------------------------------------------------------------------- full fit
+@pytest.mark.parametrize("data", CC.FULL_DATA)
+def test_full_fit_against_sklearn_spread_and_the_optimum(cl, data):
+    g = CC.golden()
+    x = g[f"full_{data}_x"]
+    v = np.sort(x.astype(np.float64))
+    for k in CC.FULL_K:
+        km = cl.KMeans1D(k, random_state=0, n_init=10).fit(x.reshape(-1, 1))
+        c = km.cluster_centers_
+        assert c.shape == (k, 1) and c.dtype == np.float32 and (np.diff(c[:, 0]) >= 0).all()
+        c = km._centres64
+        mid = (c[:-1] + c[1:]) / 2
+        b = np.concatenate([[0], np.searchsorted(v, mid, side="right"), [len(v)]])
+        J = float(((v - c[np.searchsorted(mid, v, side="left")]) ** 2).sum())
+        assert abs(km.inertia_ - J) <= 1e-12 * J
+        # a Lloyd fixed point: one more step moves no centre by more than sqrt(tol * var)
+        ps = np.concatenate([[0.0], np.cumsum(v)])
+        cnt = np.diff(b)
+        step = np.where(cnt > 0, (ps[b[1:]] - ps[b[:-1]]) / np.maximum(cnt, 1), c)
+        assert np.abs(step - c).max() <= math.sqrt(1e-4 * v.var()), (data, k)
+        lo, hi, opt = (float(g[f"full_{data}_{k}_{w}"]) for w in ("min", "max", "opt"))
+        print(f"{data} k={k}: J {J:.6g}, sklearn {lo:.6g} .. {hi:.6g}, optimum {opt:.6g}, n_iter {km.n_iter_}")
+        assert J >= opt * (1 - 1e-9), (data, k, J, opt)
+        assert J <= hi * (1 + (hi - lo) / lo), (data, k, J, lo, hi)
+        ids = km.predict(x.reshape(-1, 1))
+        assert ids.dtype == np.int64 and np.array_equal(ids, np.abs(x.astype(np.float64)[:, None] - c[None, :]).argmin(axis=1))
+
+
+# ----------------------------------------------------------------------------------------------------------- percentile
+def test_percentile_against_the_reference(cl):
+    g = CC.golden()
+    for kind in ("cont", "grid"):
+        for n in CC.PCT_N:
+            x = g[f"pct_{kind}_{n}_x"]
+            for k in CC.PCT_K:
+                m = cl.Percentile(k).fit(x.reshape(-1, 1))
+                assert m.cluster_centers_.shape == (k, 1) and m.cluster_centers_.dtype == np.float32
+                CC.check_percentile(m.cluster_centers_, g, kind, n, k)
+    # predict: the reference's rule (clip, |centre - x| in float32, first minimum), the -1 sentinels in play
+    x = g["pct_cont_257_x"]
+    m = cl.Percentile(32).fit(x.reshape(-1, 1))
+    want = np.abs(m.cluster_centers_ - x.clip(0, 1).reshape(1, -1)).argmin(axis=0)
+    assert np.array_equal(m.predict(x.reshape(-1, 1)), want)
+    assert np.array_equal(m.model().predict(torch.from_numpy(x.copy()).cuda()).cpu().numpy(), want)
+
+
+@pytest.fixture(scope="module")
+def boxes():
+    g = np.random.default_rng(42)
+    b = np.stack([g.beta(2, 2, 3000), g.random(3000), np.round(g.beta(2, 5, 3000) * 1440) / 1440, g.beta(1.5, 4, 3000)], axis=1)
+    return b.astype(np.float32)
+
+
+@pytest.fixture(scope="module")
+def fitted(cl, boxes):
+    return {alg: cl.fit_coordinate_bins(boxes, alg) for alg in ("kmeans", "percentile")}
+
+
+def test_fit_coordinate_bins_equals_the_single_fits(cl, boxes, fitted):
+    keys = [f"{c}-{k}" for k in cl.N_CLUSTERS_LIST for c in "xywh"]
+    for alg, models in fitted.items():
+        assert list(models) == keys
+        for key, m in models.items():
+            i, k = "xywh".index(key[0]), int(key[2:])
+            col = boxes[:, i:i + 1]
+            single = (cl.KMeans1D(k).fit(col) if alg == "kmeans" else cl.Percentile(k).fit(col)).model()
+            assert m.n_clusters == k and m.cluster_centers_.dtype == np.float32 and m == single, (alg, key)
+    # per cluster count (the entry point's progress lines): the same models
+    seen = []
+    again = cl.fit_coordinate_bins(boxes, "kmeans", n_clusters_list=(4, 32), progress=lambda k, s: seen.append(k))
+    assert seen == [4, 32] and all(again[key] == fitted["kmeans"][key] for key in again) and len(again) == 8
+    # the tool's subsampling: torch.randperm under manual_seed(random_state)
+    idx = torch.randperm(3000, generator=torch.Generator().manual_seed(5))[:1000].numpy()
+    sub = cl.fit_coordinate_bins(boxes, "kmeans", n_clusters_list=(8,), random_state=5, max_bbox_num=1000)
+    assert sub == cl.fit_coordinate_bins(boxes[idx], "kmeans", n_clusters_list=(8,), random_state=5)
+    assert sub != cl.fit_coordinate_bins(boxes, "kmeans", n_clusters_list=(8,), random_state=5)
+    # float64 boxes that are float32 values, on the device: the same models
+    dev64 = cl.fit_coordinate_bins(torch.from_numpy(boxes).double().cuda(), "percentile", n_clusters_list=(16,))
+    assert all(dev64[key] == fitted["percentile"][key] for key in dev64)
+
+
+def test_round_trip_through_the_tokenizer_and_the_entry_point(cl, boxes, fitted, tmp_path):
+    from layout_dm_amd import clustering_entry, task
+    from layout_dm_amd import test_entry as TE
+    from layout_dm_amd.binding import Engine
+    from layout_dm_amd.layoutdm import device_decode_plan
+
+    data = {"bbox_quantization": "kmeans", "num_bin_bboxes": 32, "shared_bbox_vocab": "x-y-w-h", "special_tokens": ["pad", "mask"],
+            "var_order": "c-x-y-w-h"}
+    dataset = {"_target_": "trainer.datasets.rico.Rico25Dataset", "max_seq_length": 25}
+    B, E = 120, 25
+    bbox = torch.from_numpy(boxes).view(B, E, 4)
+    eng = Engine(n_category=25, n_bin=32, max_elem=E, d_model=64, n_head=8, d_ff=64, n_layer=1, precision="exact", max_batch=B)
+    results = [(boxes[i * E:(i + 1) * E], np.zeros(E, np.int64)) for i in range(B)]
+    with open(tmp_path / "seed_0.pkl", "wb") as f:
+        pickle.dump({"results": results}, f)
+    for alg, models in fitted.items():
+        path = cl.save_clusters(models, str(tmp_path / alg), "rico25", 25, alg)
+        assert os.path.basename(path) == f"rico25_max25_{alg}_train_clusters.pkl"
+        tok = TE.GeometryTokenizer(TE.to_attr(dict(data, bbox_quantization=alg)), TE.to_attr(dataset), str(tmp_path / alg))
+        seq = task.encode(tok, bbox, torch.zeros((B, E), dtype=torch.long), torch.ones((B, E), dtype=torch.bool))["seq"]
+        ok, centres = device_decode_plan(tok)
+        assert ok and centres.shape == (4, 32)
+        dec = eng.decode(seq.int(), centres)
+        for i, c in enumerate("xywh"):
+            # (the tokenizers sort a model's 1-D centres when they load it, bbox_tokenizer.py:62-68: percentile's -1 sentinels
+            #  move to the front)
+            m = cl.ClusterModel(alg, np.sort(models[f"{c}-32"].cluster_centers_, axis=0))
+            ids = m.predict(boxes[:, i:i + 1])
+            assert np.array_equal(seq.view(B, E, 5)[:, :, 1 + i].reshape(-1).numpy(), ids + 25 + 32 * i), (alg, c)
+            cen = np.sort(m.cluster_centers_[:, 0].astype(np.float64))
+            assert np.array_equal(centres[i].numpy(), cen)
+            assert np.array_equal(dec["bbox"][..., i].reshape(-1).cpu().numpy(), cen[ids].clip(0, 1)), (alg, c)
+        # the entry point on the same layouts writes the same file
+        out = clustering_entry.main([str(tmp_path / "seed_0.pkl"), alg, "--dataset", "rico25", "--max_seq_length", "25",
+                                     "--result_dir", str(tmp_path / f"entry_{alg}")])
+        assert os.path.basename(out) == os.path.basename(path)
+        with open(out, "rb") as f1, open(path, "rb") as f2:
+            a, b = pickle.load(f1), pickle.load(f2)
+        assert list(a) == list(b) and all(a[key] == b[key] for key in a)
+    eng.close()
+
+
+def test_refusals_arrive_as_value_errors(cl, cuda):
+    x = np.linspace(0, 1, 100, dtype=np.float32)
+    for k in (0, 257):
+        with pytest.raises(ValueError, match="n_clusters must be in"):
+            cl.KMeans1D(k).fit(x)
+        with pytest.raises(ValueError, match="n_clusters must be in"):
+            cl.Percentile(k).fit(x)
+    with pytest.raises(ValueError, match="n = 0"):
+        cl.Percentile(2).fit(torch.empty((0, 1), device=cuda))
+    few = np.repeat(np.array([0.1, 0.2, 0.7], np.float32), 20)
+    with pytest.raises(ValueError, match="3 distinct values, fewer than n_clusters=4"):
+        cl.KMeans1D(4).fit(few)
+    with pytest.raises(ValueError, match="3 distinct values, fewer than n_clusters=4"):
+        cl.KMeans1D(4).fit(few, init=[0.1, 0.2, 0.3, 0.4])
+    with pytest.raises(ValueError, match="1 distinct values"):
+        cl.fit_coordinate_bins(np.full((50, 4), 0.5, np.float32), "kmeans", n_clusters_list=(2,))
+    assert cl.KMeans1D(3).fit(few).inertia_ == 0.0
+    one = cl.Percentile(4).fit(np.full(7, 0.5, np.float32)).cluster_centers_[:, 0]
+    assert np.array_equal(one, np.array([-1, -1, -1, 0.5], np.float32))       # all values equal: one real bin
+    for bad in (np.nan, np.inf, -np.inf):
+        y = x.copy()
+        y[37] = bad
+        for fit in (cl.KMeans1D(4).fit, cl.Percentile(4).fit):
+            with pytest.raises(ValueError, match="NaN or an infinite"):
+                fit(y)                                                            # float32: the device's error word
+            with pytest.raises(ValueError, match="NaN or an infinite"):
+                fit(y.astype(np.float64))
+    y = x.astype(np.float64)
+    y[5] = 0.1
+    with pytest.raises(ValueError, match="exactly a float32"):
+        cl.KMeans1D(4).fit(y)
+    with pytest.raises(ValueError, match="init must hold"):
+        cl.KMeans1D(4).fit(x, init=[0.1, 0.2])
