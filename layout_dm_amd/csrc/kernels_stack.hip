@@ -99,6 +99,7 @@ template <bool TM, int HEAD, bool REL = false>
 __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
   static_assert(!REL || HEAD == 2, "the relation tail belongs to the loop kernel");
   constexpr int KS = 29, STAGE = TILE_STAGE, NT2 = 15, NGV = 58;
+  using FfnRing = ldm_sched::FfnRingInterleaved;  // LDS map of the FFN ring: both stages within the ds_read offset field
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid_o = threadIdx.x;
   const int wave_o = __builtin_amdgcn_readfirstlane(tid_o >> 6);
@@ -241,8 +242,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
   };
   int t_model = 0;
   if constexpr (HEAD == 2) t_model = stack_kargs()->t_model[it];
-#pragma unroll
-  for (int i = 8; i < 16; ++i) acc[NT2 - 1][i] = to_agpr(0.f);  // columns 464..479: padding
+  static_assert(NGV == 4 * NT2 - 2, "columns 464..479 (the last two groups of tile NT2 - 1) are padding: zero, written with the gather");
   if constexpr (HEAD == 2) {
     // ------------------------------------------------------------------ prologue: x = cat_emb[token] + pos[s]
     // (nn_lib.py:204,220) gathered straight into the accumulator layout; the tables (155 x 464 and 125 x 464 floats)
@@ -269,15 +269,25 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
           rp[i] = *reinterpret_cast<const float4*>(prow + (g0 + i) * 8);
         }
       __builtin_amdgcn_sched_barrier(0);
+      // tile by tile, as whole-tuple copies into the accumulators (see LN2): defined element-wise through "=a" outputs the
+      // residual set came to lie in an AGPR range of its own, and hipcc moved all 232 registers to where the layers
+      // expect them (v_accvgpr_mov_b32) behind the gather of every step
 #pragma unroll
-      for (int i = 0; i < GB; ++i) {
-        const int gg = g0 + i;
-        if (gg < NGV) {
-          const int t = gg >> 2, q0 = (gg & 3) * 4;
-          acc[t][q0 + 0] = to_agpr(re[i].x + rp[i].x);
-          acc[t][q0 + 1] = to_agpr(re[i].y + rp[i].y);
-          acc[t][q0 + 2] = to_agpr(re[i].z + rp[i].z);
-          acc[t][q0 + 3] = to_agpr(re[i].w + rp[i].w);
+      for (int tb = 0; tb < GB / 4; ++tb) {
+        const int t = g0 / 4 + tb;
+        if (t < NT2) {
+          f32x16 tile;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int i = tb * 4 + g;
+            const bool in = t * 4 + g < NGV;  // (columns 464..479 of the last tile: padding)
+            tile[g * 4 + 0] = in ? re[i].x + rp[i].x : 0.f;
+            tile[g * 4 + 1] = in ? re[i].y + rp[i].y : 0.f;
+            tile[g * 4 + 2] = in ? re[i].z + rp[i].z : 0.f;
+            tile[g * 4 + 3] = in ? re[i].w + rp[i].w : 0.f;
+          }
+          asm volatile("" : "+a"(tile));
+          acc[t] = tile;
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -300,14 +310,21 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         if (g0 + i < NGV) raw[i] = *reinterpret_cast<const float4*>(rrow + (g0 + i) * 8);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < GB; ++i) {
-        const int gg = g0 + i;
-        if (gg < NGV) {
-          const int t = gg >> 2, q0 = (gg & 3) * 4;
-          acc[t][q0 + 0] = to_agpr(raw[i].x);
-          acc[t][q0 + 1] = to_agpr(raw[i].y);
-          acc[t][q0 + 2] = to_agpr(raw[i].z);
-          acc[t][q0 + 3] = to_agpr(raw[i].w);
+      for (int tb = 0; tb < GB / 4; ++tb) {  // (tile by tile: see the gather above)
+        const int t = g0 / 4 + tb;
+        if (t < NT2) {
+          f32x16 tile;
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int i = tb * 4 + g;
+            const bool in = t * 4 + g < NGV;
+            tile[g * 4 + 0] = in ? raw[i].x : 0.f;
+            tile[g * 4 + 1] = in ? raw[i].y : 0.f;
+            tile[g * 4 + 2] = in ? raw[i].z : 0.f;
+            tile[g * 4 + 3] = in ? raw[i].w : 0.f;
+          }
+          asm volatile("" : "+a"(tile));
+          acc[t] = tile;
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -337,7 +354,11 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         dma_first_tiles((const char*)w.img);
-        stage_tables(w, w.ada_scale, w.ada_shift, tid);
+        // (the table offsets are re-derived per layer from a thread index hipcc cannot see through: hoisted out of the
+        //  layer loop they would stay live across the streams, which fill the register file)
+        int tid_l = tid;
+        asm volatile("" : "+v"(tid_l));
+        stage_tables(w, w.ada_scale, w.ada_shift, tid_l);
         __syncthreads();
       }
       unsigned long long tE1 = 0, tE2 = 0;
@@ -492,7 +513,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
     {  // FFN chunk 0 -> stage 0 (this wave's 16 KiB); lands while LN2 runs
       const char* g0 = (const char*)w.ffn_img + wave * 16384;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) dma_lin4(voff, g0 + k * 4096, lds0 + wave * 16384 + k * 4096);
+      for (int k = 0; k < 4; ++k) dma_lin4(voff, g0 + k * 4096, lds0 + FfnRing::dma_dst(0, wave, 0) + k * 4096);
     }
     if constexpr (HEAD == 2) {
       // the NEXT consumer's attention-phase tables (every wavefront is past this layer's heads and its layer entry, the
@@ -565,11 +586,11 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
       // ---- FFN chunk loop: one continuous LDS-read / MFMA pipeline (ldm_pipes.h FfnStream)
       unsigned relW1[8], relW2[2];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) relW1[k] = r2 * RKB + ((((k << 1) | hi2) ^ (r2 & 15)) << 4);
+      for (int k = 0; k < 8; ++k) relW1[k] = ldm_sched::ffn_w1_lane(r2, hi2, k);
 #pragma unroll
-      for (int sx = 0; sx < 2; ++sx) relW2[sx] = r2 * 64 + (((2 * sx + hi2) ^ ((r2 >> 2) & 3)) << 4);
+      for (int sx = 0; sx < 2; ++sx) relW2[sx] = ldm_sched::ffn_w2_lane(r2, hi2, sx);
       const unsigned relB = lds0 + (unsigned)(reinterpret_cast<char*>(sb1) - smem) + hi2 * 16;
-      FfnStream<KS, NT2, 2, false, 6, true> F;
+      FfnStream<KS, NT2, 2, false, 6, true, FfnRing> F;
       F.xf = xf2;
       F.acc = acc;
       F.voff = voff;
@@ -579,7 +600,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) F.aW1[k] = lds0 + relW1[k];
 #pragma unroll
-      for (int sx = 0; sx < 2; ++sx) F.aW2[sx] = lds0 + relW2[sx];
+      for (int sx = 0; sx < 2; ++sx) F.aW2[sx] = lds0 + FfnRing::w2(0) + relW2[sx];
       F.ab_next = relB;
       // (same fence as in front of the head loop: every fragment back in its registers, hipcc's scoreboard drained)
 #pragma unroll
@@ -595,8 +616,11 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
       }
       // software-pipelined chunk stream (ldm_pipes.h FfnStream PIPE): iteration c = GEMM1 of chunk c + GEMM2 of chunk
       // c - 1 on stage c = W1 tile c | W2 slab c - 1 (ldm_pack::pack_ffn_image_pipelined); n_chunks + 1 iterations
+      // The loop runs two iterations per trip — stage 0, then stage 1, each a compile-time argument of its reads — and a
+      // single stage-0 iteration behind it when the count is odd (it is: 59).
       const char* fimg = (const char*)w.ffn_img;
-      for (int c = 0; c <= A.n_chunks; ++c) {
+      F.mnext = lds0 + FfnRing::dma_dst(0, wave, 0);  // (stage and 4-KiB group: literals of the M0 writes)
+      auto chunk_args = [&](int c) {
 #if !defined(LDM_ABL_FFN_WINDOW)
         F.gnext = fimg + (size_t)(c == A.n_chunks ? 0 : c + 1) * FFN_STAGE + wave * 16384;
 #elif LDM_ABL_FFN_WINDOW == 1
@@ -608,9 +632,18 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         // ... or one 16-KiB piece for all four waves, which the CU's vector L1 serves (no L2 -> CU traffic either)
         F.gnext = fimg;
 #endif
-        F.mnext = lds0 + ((c + 1) & 1) * FFN_STAGE + wave * 16384;
         F.ab_next = relB + (c + 1 >= A.n_chunks ? 0 : c + 1) * 128;
-        F.template step<0, true>();
+      };
+      int c = 0;
+      for (; c + 1 <= A.n_chunks; c += 2) {
+        chunk_args(c);
+        F.template step<0, true, 0>();
+        chunk_args(c + 1);
+        F.template step<0, true, 1>();
+      }
+      if (c <= A.n_chunks) {
+        chunk_args(c);
+        F.template step<0, true, 0>();
       }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -702,6 +735,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
       // ---- the step's tail in the same workgroup.  The five 32-class tiles stay in the (dead) residual accumulators;
       // when the last one is done the weight ring is free and takes the layout's logits as [token][kPostLd] floats.
       constexpr int NHT = 5;  // launcher: n_head_tiles == 5
+      constexpr int NA = 5;   // launcher: n_attr == 5 (c x y w h)
 #pragma unroll
       for (int ht = 0; ht < NHT; ++ht) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -738,7 +772,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
           const f32x16 tile = acc[ht];
 #pragma unroll
           for (int i = 0; i < 16; ++i)
-            if (ht * 32 + (i >> 2) * 8 + hi3 * 4 + (i & 3) < Cm1) {
+            if (ht < NHT - 1 || ht * 32 + (i >> 2) * 8 + hi3 * 4 + (i & 3) < Cm1) {  // (launcher: C - 1 > 128 = 32 (NHT - 1))
               mx = fmaxf(mx, tile[i]);
               am = fmaxf(am, fabsf(tile[i]));
             }
@@ -752,7 +786,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
           const f32x16 tile = acc[ht];
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            if (ht * 32 + (i >> 2) * 8 + hi3 * 4 + (i & 3) < Cm1) se += __expf(tile[i] - mx);
+            if (ht < NHT - 1 || ht * 32 + (i >> 2) * 8 + hi3 * 4 + (i & 3) < Cm1) se += __expf(tile[i] - mx);
             mine[ht * 32 + (i >> 2) * 8 + (i & 3)] = tile[i];
           }
         }
@@ -760,14 +794,14 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         if (hi3 == 0) rstat[row3] = make_float4(mx, __logf(se), am, 0.f);
         // the step's schedule scalars of every attribute (constrained.py:81-90,114)
         const int T1 = p.T + 1, u = (t_post - 1 + T1) % T1;
-        if (lane3 < p.v.n_attr * 10) {
+        if (lane3 < NA * 10) {
           const int at = lane3 / 10, k = lane3 - at * 10;
           const int kind = k == 0 ? kLogAt : k == 1 ? kLogBt : k == 2 ? kLogCt : k == 3 ? kLogCumAt : k == 4 ? kLogCumBt
                          : k == 5 ? kLogCumCt : k == 6 ? kLogCumAt : k == 7 ? kLogCumBt : k == 8 ? kLogCumCt : kLog1mCumCt;
-          ssch[lane3] = p.sched[((size_t)kind * p.v.n_attr + at) * T1 + (k < 6 ? t_post : u)];
+          ssch[lane3] = p.sched[((size_t)kind * NA + at) * T1 + (k < 6 ? t_post : u)];
         }
         // ... and the body of every attribute's sub-vocabulary (indexed per lane below: from LDS, not from a private copy)
-        if (lane3 < p.v.n_attr) {
+        if (lane3 < NA) {
           reinterpret_cast<int*>(ssch)[100 + 2 * lane3] = p.v.start[lane3];
           reinterpret_cast<int*>(ssch)[101 + 2 * lane3] = p.v.count[lane3];
         }
@@ -780,7 +814,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         // q(x_t | x_0), q(x_t | x_{t-1}) per (attribute, x_t is / is not [MASK]): ten variants per step instead of one
         // evaluation (12 transcendentals) per token
         const int lane5 = stack_lane_id();
-        if (lane5 < 2 * p.v.n_attr) {
+        if (lane5 < 2 * NA) {
           const float* sc10 = ssch + (lane5 >> 1) * 10;
           const ldm_post::StepSchedule sc{sc10[0], sc10[1], sc10[2], sc10[3], sc10[4],
                                           sc10[5], sc10[6], sc10[7], sc10[8], sc10[9]};
@@ -808,7 +842,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         for (int rd = 0; rd < 8; ++rd) {
           const int s = wave * 32 + rd * 4 + grp;
           if (s < S) {
-            const int attr = s % p.v.n_attr;
+            const int attr = s % NA;
             const float* sc10 = ssch + attr * 10;
             const ldm_post::StepSchedule sc{sc10[0], sc10[1], sc10[2], sc10[3], sc10[4],
                                             sc10[5], sc10[6], sc10[7], sc10[8], sc10[9]};
@@ -835,7 +869,7 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
             ta.seed = p.rng[0];
             bool shortcut = ldm_post::strong_shortcut(ta);  // conditioned token: every sampler returns it (ldm_post_token.h)
             // (... unless the SGD moves its row: a strong-masked bbox token of a graph node, kernels_relation.hip)
-            if constexpr (REL) shortcut = shortcut && !(adjust && attr != 0 && node_of[s / p.v.n_attr] > 0);
+            if constexpr (REL) shortcut = shortcut && !(adjust && attr != 0 && node_of[s / NA] > 0);
             if (shortcut) {
               if (g.lane() == 0) {
                 toks[s] = ta.cond_tok;

@@ -18,6 +18,12 @@ constexpr int kLnDp = 512;  // LDS parameter image: multiplier at [0, kLnDp), sh
 __device__ __forceinline__ void dma_set_m0(unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %0" ::"s"(lds_addr) : "memory");
 }
+// M0 = base + literal: destinations that differ by compile-time offsets share ONE SGPR (hipcc otherwise keeps every
+// hoisted sum in a register of its own for the whole kernel)
+template <unsigned OFF>
+__device__ __forceinline__ void dma_set_m0_add(unsigned lds_addr) {
+  asm volatile("s_add_u32 m0, %0, %1" ::"s"(lds_addr), "n"(OFF) : "memory", "scc");
+}
 template <int OFF>
 __device__ __forceinline__ void dma_lin(unsigned voff, const char* sbase) {
   asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" ::"v"(voff), "s"(sbase), "n"(OFF) : "memory");

@@ -202,7 +202,8 @@ bool ldm_host::loop_fusable(const ldm_handle* h, const ldm_relation* rel) {
   if (rel && (h->rel_loop == 0 || h->cfg.q_type != LDM_Q_CONSTRAINED || h->cfg.n_bin > 32 || h->cfg.max_elem > 32 ||
               h->cfg.n_attr != 5))
     return false;
-  return h->stack_loop && h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6 && h->head_img_ks && h->Cp == 160 && live_max <= kStackPostMaxLive && h->S <= 128 &&
+  // (C - 1 > 128: the row log-softmax guards `class < C - 1` in the last of the five head tiles only; n_attr == 5 is ldm_create's)
+  return h->stack_loop && h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6 && h->head_img_ks && h->Cp == 160 && h->C - 1 > 128 && live_max <= kStackPostMaxLive && h->S <= 128 &&
          h->T < 32768 && !h->fast.empty() && h->tbl_att_dyn && h->D == 464 && h->F <= 2048;
 }
 

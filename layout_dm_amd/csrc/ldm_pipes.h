@@ -180,7 +180,13 @@ __device__ __forceinline__ f16x8 cvt8(const f32x16& a, const float4& b0, const f
 // chunk i is issued in the shadows of that GEMM2's MFMAs 2..9: pf = fragments of chunk i - 1 (in use), pfn = fragments
 // of chunk i (being built), copied at the top of the next iteration.  The LDS traffic, its order and every counted wait
 // are unchanged (ldm_stream_sched.h).
-template <int KS, int NT2, int DE, bool TM, int PFQ = 6, bool PIPE = false>
+// MAP (ldm_stream_sched.h): where the two ring stages lie in LDS.  FfnRingLinear: image order, the per-lane addresses
+// toggled between the stages as described above.  FfnRingInterleaved (the stack kernel): both stages of either half
+// within the ds_read offset field of ONE address, so aW1 / aW2 are computed once per FFN phase and never modified; the
+// stage ST of the chunk a step belongs to is a compile-time argument (the chunk loop is unrolled by two: ST = 0, 1),
+// items >= NIT read stage ST ^ 1 through the immediate, and with PIPE the halves swap the roles of pf and pfn instead
+// of copying one into the other — per chunk 10 v_xor and 8 v_mov less beside 59 MFMAs, same reads, same order.
+template <int KS, int NT2, int DE, bool TM, int PFQ = 6, bool PIPE = false, class MAP = ldm_sched::FfnRingLinear>
 struct FfnStream {
   using SCH = ldm_sched::FfnSched<KS, NT2, PFQ>;  // (replayed on the CPU: tests/cpu_sched_check.cpp)
   static constexpr int PF = SCH::PF;   // queue depth.  r02: depth 10 instead of 6 changes nothing (profiles/r02_call21_*)
@@ -198,18 +204,30 @@ struct FfnStream {
   const char* gnext;
   unsigned mnext, voff, ab_next;
 
-  template <int J>
+  // (immediate-stage map: mnext = ring base + this wave's piece 0 of STAGE 0, set once per FFN phase; the stage and the
+  //  4-KiB group are a literal of the s_add that writes M0 — no SGPR per destination)
+  template <int J, int ST>
   __device__ __forceinline__ void dma_m0() {
-    if constexpr (J < IPW && (J & 3) == 0) dma_set_m0(mnext + (J >> 2) * 4096);
+    if constexpr (J < IPW && (J & 3) == 0) {
+      if constexpr (MAP::kStageInImm) dma_set_m0_add<MAP::dma_dst(ST ^ 1, 0, 0) + (J >> 2) * 4096>(mnext);
+      else dma_set_m0(mnext + (J >> 2) * 4096);
+    }
   }
   template <int J>
   __device__ __forceinline__ void dma_slot() {
     if constexpr (J < IPW) dma_lin<(J & 3) * 1024>(voff, gnext + (J >> 2) * 4096);
   }
-  template <int IT>  // IT in [0, NIT + PF): items >= NIT belong to the next chunk
+  template <int IT, int ST = 0>  // IT in [0, NIT + PF): items >= NIT belong to the next chunk
   __device__ __forceinline__ void read_item() {
     constexpr int I = IT % NIT;
-    if constexpr (I < KS) {
+    if constexpr (MAP::kStageInImm) {
+      constexpr int s = IT >= NIT ? (ST ^ 1) : ST;
+      constexpr unsigned off = MAP::template imm<KS, NT2>(I, s);
+      static_assert(off < 65536u, "ds_read offset field");
+      if constexpr (I < KS) dsr128<off>(q[IT % PF], aW1[I & 7]);
+      else if constexpr (I == KS) dsr128<off>(q[IT % PF], aW1[0]);  // pseudo item
+      else dsr128<off>(q[IT % PF], aW2[(I - KS - 1) / NT2]);
+    } else if constexpr (I < KS) {
       dsr128<256 * (I >> 3)>(q[IT % PF], aW1[I & 7]);
     } else if constexpr (I == KS) {
       dsr128<0>(q[IT % PF], aW1[0]);  // pseudo item (ReLU step): keeps the slot / count bookkeeping uniform
@@ -224,8 +242,13 @@ struct FfnStream {
     dsr128f<64>(bb[2], ab_next);
     dsr128f<96>(bb[3], ab_next);
   }
-  template <int IT, bool DMA>
+  template <int IT, bool DMA, int ST = 0>
   __device__ __forceinline__ void step() {
+    static_assert(ST == 0 || MAP::kStageInImm, "the stage is a compile-time argument only where the map encodes it in the immediate");
+    // PIPE on an immediate-stage map: odd chunks multiply by pfn and build into pf (no copy at the top of a chunk)
+    constexpr bool SWP = PIPE && MAP::kStageInImm && ST == 1;
+    f16x8(&pcur)[2] = SWP ? pfn : pf;
+    [[maybe_unused]] f16x8(&pnew)[2] = SWP ? pf : pfn;
     if constexpr (IT < NIT) {
       // LDS operations younger than item IT when it is waited for: PF - 1 items, + the 4 bias reads issued at SYNC
       wait_lgkm<SCH::after(IT)>();
@@ -266,7 +289,7 @@ struct FfnStream {
         }
       } else {
         constexpr int sx = (IT - KS - 1) / NT2, t = (IT - KS - 1) % NT2;
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur, pf[sx], acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur, pcur[sx], acc[t], 0, 0, 0);
         if constexpr (PIPE) {
           // bias (inside chain A) + ReLU + cast of the GEMM1 that finished >= 3 MFMAs (96 cycles) ago, one accumulator
           // pair per MFMA shadow: add, add, cvt_pk, pk_max — scalar adds, packed f32 VALU is slow beside MFMAs
@@ -278,12 +301,12 @@ struct FfnStream {
             f16x2v hv = {(_Float16)s0, (_Float16)s1};
             const f16x2v zero = {(_Float16)0.f, (_Float16)0.f};
             hv = __builtin_elementwise_max(hv, zero);
-            pfn[i >> 2][(i & 3) * 2 + 0] = hv[0];
-            pfn[i >> 2][(i & 3) * 2 + 1] = hv[1];
+            pnew[i >> 2][(i & 3) * 2 + 0] = hv[0];
+            pnew[i >> 2][(i & 3) * 2 + 1] = hv[1];
           }
         }
       }
-      if constexpr (PIPE && IT == 0) {  // the fragments finished during the previous GEMM2 (which no longer reads pf)
+      if constexpr (PIPE && IT == 0 && !MAP::kStageInImm) {  // the fragments finished during the previous GEMM2 (which no longer reads pf)
         pf[0] = pfn[0];
         pf[1] = pfn[1];
       }
@@ -301,18 +324,20 @@ struct FfnStream {
           t_sync += tB - tA;
         }
         read_bias();
+        if constexpr (!MAP::kStageInImm) {
 #pragma unroll
-        for (int sx = 0; sx < 2; ++sx) aW2[sx] ^= 0x10000u;  // (last W2 read of this chunk was issued at step SYNC - 1)
+          for (int sx = 0; sx < 2; ++sx) aW2[sx] ^= 0x10000u;  // (last W2 read of this chunk was issued at step SYNC - 1)
+        }
       }
-      read_item<IT + PF>();
-      if constexpr (IT == KS - 1 - PF) {
+      read_item<IT + PF, ST>();
+      if constexpr (IT == KS - 1 - PF && !MAP::kStageInImm) {
         // item KS - 1 (the last W1 fragment of this chunk) has just been issued: aW1 now points into the next stage
 #pragma unroll
         for (int k = 0; k < 8; ++k) aW1[k] ^= 0x10000u;
       }
       if constexpr (DMA && IT % DE == DE - 1) dma_slot<IT / DE>();
-      else if constexpr (DMA && IT % DE == 0) dma_m0<IT / DE>();
-      step<IT + 1, DMA>();
+      else if constexpr (DMA && IT % DE == 0) dma_m0<IT / DE, ST>();
+      step<IT + 1, DMA, ST>();
     }
   }
   template <int IT>

@@ -64,4 +64,53 @@ struct FfnSched {
   static constexpr int after(int IT) { return IT > SYNC ? PF - 1 + 4 : PF - 1; }
 };
 
+// The LDS map of FfnStream's two-stage ring (128 KiB at the ring base).  A stage holds one 64-KiB chunk of the global
+// image: the W1 tile (32 rows of 1 KiB) in image bytes [0, 32 KiB), the W2 slab (NT2 tiles of 2 KiB) behind it.  Wave w
+// copies image bytes [w * 16 KiB, (w + 1) * 16 KiB) of a stage as 16 pieces of 1 KiB.  A fragment read is
+// ds_read_b128 at (per-lane register) + (16-bit immediate): the register holds reg_base(I) + the lane part (W1: below
+// 32 KiB, per fragment column; W2: below 2 KiB), the immediate selects the fragment row group / tile — and, where the
+// map allows it, the STAGE.
+//
+// Lane parts (r = lane & 31: weight row of the fragment, hi = lane >> 5: k-half), bank swizzle as packed on the host:
+constexpr unsigned ffn_w1_lane(int r, int hi, int k) { return (unsigned)(r * 1024 + ((((k << 1) | hi) ^ (r & 15)) << 4)); }    // column k = I & 7
+constexpr unsigned ffn_w2_lane(int r, int hi, int sx) { return (unsigned)(r * 64 + (((2 * sx + hi) ^ ((r >> 2) & 3)) << 4)); }  // k16-step sx
+//
+// FfnRingLinear (the hybrid kernel): stage s = [s * 64 KiB, (s + 1) * 64 KiB), image order.  The stage offset 0x10000
+// does not fit the offset field, so the registers are toggled in place (address ^ 0x10000) once per chunk.
+struct FfnRingLinear {
+  static constexpr bool kStageInImm = false;
+  static constexpr unsigned kHalf = 0x8000u, kRing = 0x20000u;
+  static constexpr unsigned w1(int s) { return (unsigned)s * 0x10000u; }
+  static constexpr unsigned w2(int s) { return (unsigned)s * 0x10000u + kHalf; }
+  static constexpr unsigned dma_dst(int s, int w, int k) { return (unsigned)s * 0x10000u + (unsigned)w * 0x4000u + (unsigned)k * 1024u; }
+  // register base / immediate of queue item I (I < KS: W1 fragment, I == KS: pseudo item, else W2 fragment) in stage s;
+  // s != 0 is reached through the toggled register, i.e. imm(I, 1) - imm(I, 0) = 0x10000 is NOT encodable
+  template <int KS, int NT2>
+  static constexpr unsigned reg_base(int) { return 0u; }
+  template <int KS, int NT2>
+  static constexpr unsigned imm(int I, int s) {
+    return (unsigned)s * 0x10000u + (I < KS ? 256u * (unsigned)(I >> 3) : I == KS ? 0u : kHalf + (unsigned)((I - KS - 1) % NT2) * 2048u);
+  }
+};
+// FfnRingInterleaved (the stack kernel): the halves of the two stages interleave — W1 of stage s at s * 32 KiB, W2 of
+// stage s at 64 KiB + s * 32 KiB — so that BOTH stages of either half are within the offset field of one register:
+// W1 immediates <= 0x8000 + 768, W2 immediates <= 0x8000 + 14 * 2048 = 61 440 on a register that carries the 64 KiB.
+// The registers are then loop invariants and the stage is a compile-time argument of every read.
+struct FfnRingInterleaved {
+  static constexpr bool kStageInImm = true;
+  static constexpr unsigned kHalf = 0x8000u, kRing = 0x20000u;
+  static constexpr unsigned w1(int s) { return (unsigned)s * kHalf; }
+  static constexpr unsigned w2(int s) { return 0x10000u + (unsigned)s * kHalf; }
+  // waves 0, 1 carry the W1 tile, waves 2, 3 the W2 slab
+  static constexpr unsigned dma_dst(int s, int w, int k) {
+    return (unsigned)(w >> 1) * 0x10000u + (unsigned)s * kHalf + (unsigned)(w & 1) * 0x4000u + (unsigned)k * 1024u;
+  }
+  template <int KS, int NT2>
+  static constexpr unsigned reg_base(int I) { return I <= KS ? 0u : 0x10000u; }
+  template <int KS, int NT2>
+  static constexpr unsigned imm(int I, int s) {
+    return (unsigned)s * kHalf + (I < KS ? 256u * (unsigned)(I >> 3) : I == KS ? 0u : (unsigned)((I - KS - 1) % NT2) * 2048u);
+  }
+};
+
 }  // namespace ldm_sched

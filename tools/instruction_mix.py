@@ -6,7 +6,9 @@ and per instruction class, from its gfx950 assembly (VERDICT r3 next #6 i).
 How: hipcc -S, the kernel's basic blocks with LLVM's loop annotations ("Loop Header: Depth=n", "in Loop: Header=..."), and
 the trip counts of the reference backbone (4 layers, 8 heads, 59 pipelined FFN iterations, 8 tail rounds unrolled by 2).
 Loops are recognised by their MFMA signature — the head loop holds 266 MFMAs per wave (6 x 29 in_proj + 32 attention +
-60 out-projection), the FFN loop 59 (29 GEMM1 + 30 GEMM2), the vocabulary head 145 (5 x 29) — and the weighted MFMA
+60 out-projection), the FFN loop 118 (two pipelined iterations of 29 GEMM1 + 30 GEMM2: 29 trips, and the odd 59th
+iteration as straight-line code of the layer loop behind it; trees before the interleaved FFN ring: one iteration of 59
+per trip), the vocabulary head 145 (5 x 29) — and the weighted MFMA
 total is checked against the algorithmic count (22 581 per wave and reverse step = what SQ_INSTS_VALU_MFMA_MOPS / 16
 measured on the MI355X: profiles/r03_final2_sq_counters_fast_loop.txt: 4.6246e9 per 512 x 100 x 4 waves).
 
@@ -104,15 +106,8 @@ def loop_of(b):
     return None, 0
 
 
-def main():
-    asm = None
-    if "--asm" in sys.argv:
-        asm = sys.argv[sys.argv.index("--asm") + 1]
-    else:
-        asm = "/tmp/ldm_stack_mix.s"
-        src = os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_stack.hip")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
-                        "-S", "-o", asm, src, "-Wno-unused-function"], check=True, stderr=subprocess.DEVNULL)
+def mix(asm):
+    """(phase -> Counter of instruction classes, Counter of the totals) of the loop kernel in the assembly file `asm`."""
     blocks = parse(asm)
     # loop membership and MFMA totals per loop
     parent = {}
@@ -127,14 +122,19 @@ def main():
             mf[hdr] += sum(1 for op, _ in b["ins"] if op.startswith("v_mfma"))
     step = next(b["loop"] for b in blocks if b["depth"] == 1 and "Loop Header" in b["hdr"])
     head = next(h for h, n in mf.items() if n == 266)
-    ffn = next(h for h, n in mf.items() if n == 59)
+    ffn = next((h for h, n in mf.items() if n == 118), None)   # the double iteration (FfnRingInterleaved) ...
+    ffn_trips = N_CHUNK_IT // 2
+    if ffn is None:                                            # ... or the single one of the trees before it
+        ffn, ffn_trips = next(h for h, n in mf.items() if n == 59), N_CHUNK_IT
+    else:
+        assert N_CHUNK_IT % 2 == 1 and mf[parent[ffn]] == 59, "the odd iteration belongs to the layer loop"
     layer = parent[head]
     assert parent[ffn] == layer and parent[layer] == step, (parent, head, ffn, layer, step)
     # the tail loop: the depth-2 loop of the step loop behind the layer loop that holds no MFMA
     order = [b["loop"] for b in blocks]
     tail = next(b["loop"] for b in blocks[order.index(layer):] if b["depth"] == 2 and "Loop Header" in b["hdr"]
                 and b["loop"] != layer and mf[b["loop"]] == 0 and sum(len(x["ins"]) for x in blocks if x["loop"] == b["loop"]) > 500)
-    trips = {step: 1, layer: N_LAYER, head: N_HEAD, ffn: N_CHUNK_IT, tail: TAIL_ROUNDS // 2}
+    trips = {step: 1, layer: N_LAYER, head: N_HEAD, ffn: ffn_trips, tail: TAIL_ROUNDS // 2}
 
     def weight(hdr):
         w, h = 1.0, hdr
@@ -167,9 +167,7 @@ def main():
         elif layer in chain:
             seen_layer = True
             ph = ("layer entry (row statistics, AdaLN transform, tables)" if not seen_head else
-                  "LN2 + FFN entry" if not seen_ffn else "layer exit")
-            if seen_ffn and ph == "layer exit":
-                pass
+                  "LN2 + FFN entry" if not seen_ffn else "FFN odd last iteration + layer exit")
         else:
             ph = ("step prologue (embedding gather)" if not seen_layer else
                   "vocabulary head (LN + 5 tiles) + row log-softmax" if not seen_tail else "step epilogue")
@@ -181,11 +179,27 @@ def main():
     total = collections.Counter()
     for c in phases.values():
         total.update(c)
+    assert abs(total["mfma"] - 22581) < 1, total["mfma"]
+    return phases, total
+
+
+def valu_total(total):
+    return sum(total[k] for k in CLASSES if k.startswith("valu"))
+
+
+def main():
+    if "--asm" in sys.argv:
+        asm = sys.argv[sys.argv.index("--asm") + 1]
+    else:
+        asm = "/tmp/ldm_stack_mix.s"
+        src = os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_stack.hip")
+        subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
+                        "-S", "-o", asm, src, "-Wno-unused-function"], check=True, stderr=subprocess.DEVNULL)
+    phases, total = mix(asm)
     valu = [k for k in CLASSES if k.startswith("valu")]
     print("# dynamic instruction mix of stack_stream_k<false,2> per WAVEFRONT and reverse step (sampling=random), from the gfx950")
     print("# assembly of this tree's kernels_stack.hip weighted by the loop trip counts (tools/instruction_mix.py)")
     print(f"# MFMA check: {total['mfma']:.0f} per wave-step (algorithmic + padding: 32 x 266 + 236 x 59 + 145 = 22581)")
-    assert abs(total["mfma"] - 22581) < 1, total["mfma"]
     hdr = f"{'phase':58s}" + "".join(f"{k.replace('valu_', 'v:'):>11s}" for k in CLASSES) + f"{'VALU/MFMA':>11s}"
     print(hdr)
     for ph, c in phases.items():
