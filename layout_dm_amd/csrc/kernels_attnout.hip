@@ -40,23 +40,25 @@
 #include "ldm_dma.h"
 #include "ldm_kernels.h"
 #include "ldm_pipes.h"
+#include "ldm_x3_sched.h"
 
 namespace ldm {
+
+// ldm_x3_sched.h: the LDS map (AO_KH .. AO_LDS), the per-lane address functions, the ring's slot arithmetic and the six counted
+// waits per head (AO_UNIT, AO_WAIT_*) — dumped on the host by tests/cpu_x3_sched_check.cpp for tests/test_attnout_layout.py
+using namespace ldm_sched;
 
 namespace {
 
 typedef __fp16 ao_h16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef _Float16 ao_f16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int AO_KH = 0, AO_VH = 32768, AO_RING = 65536, AO_SLOT = 32768, AO_LO = 16384;   // K lo / V lo at + AO_LO
-constexpr int AO_LDS = AO_RING + 3 * AO_SLOT;   // 163 840
-static_assert(AO_LDS <= 160 * 1024, "LDS budget");
 constexpr int AO_NT = 15;                        // 32-column output tiles
 constexpr int AO_RD = 2;                         // LDS read pipeline: fragments requested this many (3-MFMA) items ahead
 constexpr int AO_RDP = 1;                        // ... in the P V phase: this many (6-MFMA) key steps ahead
-constexpr int AO_UNIT = 8;                       // DMA pieces (1 KiB) per wave and unit (K, V, one ring stage) — the counted waits below
 
-// one DMA unit = 8 pieces of this wave: two groups of four (one M0 write each)
+// one DMA unit = AO_UNIT = 8 pieces of this wave: two groups of four (one M0 write each)
+static_assert(AO_UNIT == 8, "ao_dma8, load_q and dma_prow issue eight vector-memory instructions each");
 __device__ __forceinline__ void ao_dma8(unsigned voff, const char* g0, unsigned l0, const char* g1, unsigned l1) {
   dma_lin4(voff, g0, l0);
   dma_lin4(voff, g1, l1);
@@ -223,24 +225,22 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
 
   // ---- addresses
   // K / V whole-head DMA, 16 + 16 pieces of 1 KiB (16 keys x 64 B of one panel) per operand: wave w moves pieces 4 w .. 4 w + 3 of the
-  // hi and of the lo image = panel w >> 1, keys 64 (w & 1) + 16 j.  LDS slot l of a piece receives
-  //   K: key l >> 2, logical chunk (l & 3) ^ ((key >> 2) & 3)        V: key 4 (l >> 4) + ((l >> 1) & 3), chunk 2 ((l >> 3) & 1) + (l & 1)
+  // hi and of the lo image = panel w >> 1, keys 64 (w & 1) + 16 j; the per-lane source offsets permute the piece's chunks (ao_voff_k / _v)
   const unsigned lu = (unsigned)lane;
-  const unsigned voff_k = ((lu >> 2) << 6) | (((lu & 3u) ^ ((lu >> 4) & 3u)) << 4);
-  const unsigned voff_v = ((4u * (lu >> 4) + ((lu >> 1) & 3u)) << 6) | ((2u * ((lu >> 3) & 1u) + (lu & 1u)) << 4);
+  const unsigned voff_k = LDM_AO_VOFF_K(lu);
+  const unsigned voff_v = LDM_AO_VOFF_V(lu);
   const unsigned voff_lin = lu * 16;
   // per head: panels (which * 8 + head) * 2 + (wave >> 1), rows row0 + 64 (wave & 1) ..
   const char* gq_hi = a.qkv_hi + row0 * 64;               // + panel * PS
   const char* gq_lo = a.qkv_lo + row0 * 64;
-  // fragment addresses (LDS bytes).  K rows by (m, g): + (ks >> 1) * 8 KiB + kt * 2 KiB, chunk (2 (ks & 1) + g) ^ ((m >> 2) & 3);
-  // Wo stage rows by (m, g): 32-byte rows, chunk g ^ ((m >> 3) & 1)
-  const unsigned a_k0 = ((unsigned)m << 6) | ((((unsigned)g) ^ (((unsigned)m >> 2) & 3u)) << 4);           // even k16-steps
-  const unsigned a_k1 = ((unsigned)m << 6) | (((2u + (unsigned)g) ^ (((unsigned)m >> 2) & 3u)) << 4);      // odd k16-steps
-  const unsigned a_row = ((unsigned)m << 5) | ((((unsigned)g) ^ (((unsigned)m >> 3) & 1u)) << 4);
+  // fragment addresses (LDS bytes).  K rows by (m, g): + (ks >> 1) * 8 KiB + kt * 2 KiB + the swizzled chunk of ao_a_k; Wo stage rows: ao_a_row
+  const unsigned a_k0 = ao_a_k_mg((unsigned)m, (unsigned)g, 0);           // even k16-steps
+  const unsigned a_k1 = ao_a_k_mg((unsigned)m, (unsigned)g, 1);           // odd k16-steps
+  const unsigned a_row = ao_a_row_mg((unsigned)m, (unsigned)g);
   // V transpose reads: lane l at + 8 l of the 512-byte run of (d tile, 8 keys)
   const unsigned a_v = lds0 + lu * 8;
   // Q fragments: this lane's row of panel ks >> 1, chunk 2 (ks & 1) + g
-  const unsigned voff_q = (unsigned)q * 64u + (unsigned)g * 16u;
+  const unsigned voff_q = LDM_AO_VOFF_Q((unsigned)q, (unsigned)g);
 
   auto dma_kv = [&](int head, int which, unsigned lds_hi) {   // K (which = 1) / V (which = 2) of `head`: this wave's 4 + 4 pieces, hi then lo
     const size_t pn = (size_t)((which * 8 + head) * 2 + (wave >> 1));
@@ -271,17 +271,18 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
       // names the layout's last real row from this wave's base — in SIGNED arithmetic (r06 fix: the unsigned product sent S = 50's
       // waves 2 / 3 four gigabytes up; tests/test_hip_parity.py short_sequence passed or faulted with the process's memory map)
       const int r = r0v + j, rr = r < nrow ? r : nrow - 1;
-      unsigned lc = lu ^ (unsigned)((r0 + j) & 15);                              // logical chunk that lands in physical chunk `lane`
+      unsigned lc = ao_row_chunk(lu, (unsigned)(r0 + j));                        // logical chunk that lands in physical chunk `lane`
       if (half == 1) lc = lc < 52u ? lc : 51u;                                   // (chunks beyond the row: a valid chunk again, never read)
       const char* src = pres + (long)rr * (long)(ND * 4) + half * 1024;
       asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lc * 16u), "s"(src), "s"(lds_base + (unsigned)j * 1024u) : "memory");
     }
   };
-  // where the epilogue finds them (absolute LDS byte addresses of this wave's 8-row groups; ring slots of head 7: (4 * 7) % 3 = 1 -> stage 1 in slot
-  // 2, stage 2 in slot 0, stage 3 in slot 1: tests/test_attnout_layout.py replays the slot arithmetic)
-  const unsigned grpA[4] = {lds0 + AO_KH + wave * 8192u, lds0 + AO_VH + wave * 8192u, lds0 + AO_RING + 2u * AO_SLOT + wave * 8192u,
-                            lds0 + AO_RING + 0u * AO_SLOT + wave * 8192u};
-  const unsigned grpB0 = lds0 + AO_RING + 1u * AO_SLOT + wave * 8192u;
+  // where the epilogue finds them (absolute LDS byte addresses of this wave's 8-row groups; the ring slots are those of head 7's stages 1, 2, 3:
+  // 2, 0, 1 — the slots the head loop's refills behind Bd2, Bd3 and Ba name at h == 7)
+  constexpr unsigned kSl1 = ao_ring_slot(4 * 7 + 1), kSl2 = ao_ring_slot(4 * 7 + 2), kSl3 = ao_ring_slot(4 * 7 + 3);
+  const unsigned grpA[4] = {lds0 + AO_KH + wave * 8192u, lds0 + AO_VH + wave * 8192u, lds0 + AO_RING + kSl1 * AO_SLOT + wave * 8192u,
+                            lds0 + AO_RING + kSl2 * AO_SLOT + wave * 8192u};
+  const unsigned grpB0 = lds0 + AO_RING + kSl3 * AO_SLOT + wave * 8192u;
 
   f16x8 qh[4], ql[4];
   auto load_q = [&](int head) {                                // 8 asm loads = one DMA unit's worth in the counted waits
@@ -337,7 +338,7 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
   dma_w(0, 0);
   dma_w(0, 0);
   dma_w(1, 1);
-  ao_sync<4 * AO_UNIT, TM>(&tw[0], &tb[0]);      // Ba(0): Q_0, K_0 landed (behind them: V_0, dummy, W_0,0, W_0,1)
+  ao_sync<AO_WAIT_BA * AO_UNIT, TM>(&tw[0], &tb[0]);      // Ba(0): Q_0, K_0 landed (behind them: V_0, dummy, W_0,0, W_0,1)
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qh[ks]), "+v"(ql[ks]));
   dma_w(2, 2);
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
 #pragma nounroll
   for (int h = 0; h < 8; ++h) {
     // ---- Bb(h): V_h landed (behind it: W_h-1,3  W_h,0  W_h,1  W_h,2); every wave is through with K_h
-    ao_sync<4 * AO_UNIT, TM>(&tw[1], &tb[1]);
+    ao_sync<AO_WAIT_BB * AO_UNIT, TM>(&tw[1], &tb[1]);
     load_q(h + 1);
     if (h < 7) dma_kv(h + 1, 1, AO_KH);
     else dma_prow(0, 0, grpA[0]);
@@ -439,26 +440,26 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
       }
     AO_T1(2);
     // ---- Bc(h): W_h,0 landed (behind it: W_h,1  W_h,2  Q_h+1 K_h+1); every wave is through with V_h
-    ao_sync<4 * AO_UNIT, TM>(&tw[2], &tb[2]);
+    ao_sync<AO_WAIT_BC * AO_UNIT, TM>(&tw[2], &tb[2]);
     if (h < 7) dma_kv(h + 1, 2, AO_VH);
     else dma_prow(0, 8, grpA[1]);
     // ---- the head's four out_proj stages: out^T tile t += Wo[32 t .., k16-step] · O   (hi·hi + hi·lo + lo·hi)
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
       if (st == 1) {          // Bd1: W_h,1 landed (behind it: W_h,2  Q K_h+1  V_h+1); stage 0's slot is free -> W_h,3
-        ao_sync<4 * AO_UNIT, TM>(&tw[3], &tb[3]);
-        dma_w(4 * h + 3, slot);
+        ao_sync<AO_WAIT_BD1 * AO_UNIT, TM>(&tw[3], &tb[3]);
+        dma_w(4 * h + 3, ao_slot_at(slot, 3));
       } else if (st == 2) {   // Bd2: W_h,2 landed (behind it: Q K_h+1  V_h+1  W_h,3); stage 1's slot -> W_h+1,0
-        ao_sync<4 * AO_UNIT, TM>(&tw[4], &tb[4]);
-        if (h < 7) dma_w(4 * h + 4, slot == 2 ? 0 : slot + 1);
+        ao_sync<AO_WAIT_BD2 * AO_UNIT, TM>(&tw[4], &tb[4]);
+        if (h < 7) dma_w(4 * h + 4, ao_slot_at(slot, 4));
         else dma_prow(0, 16, grpA[2]);
       } else if (st == 3) {   // Bd3: W_h,3 landed (behind it: W_h+1,0); stage 2's slot -> W_h+1,1
-        ao_sync<1 * AO_UNIT, TM>(&tw[5], &tb[5]);
-        if (h < 7) dma_w(4 * h + 5, slot == 0 ? 2 : slot - 1);
+        ao_sync<AO_WAIT_BD3 * AO_UNIT, TM>(&tw[5], &tb[5]);
+        if (h < 7) dma_w(4 * h + 5, ao_slot_at(slot, 5));
         else dma_prow(0, 24, grpA[3]);
       }
       AO_T0();
-      const int sl_st = st == 0 ? slot : st == 1 ? (slot == 2 ? 0 : slot + 1) : st == 2 ? (slot == 0 ? 2 : slot - 1) : slot;
+      const int sl_st = ao_slot_at(slot, st);
       const unsigned aw = lds0 + AO_RING + (unsigned)sl_st * AO_SLOT + a_row;
       f16x8 wh[AO_RD + 1], wl[AO_RD + 1];
 #pragma unroll
@@ -485,12 +486,12 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
       }
       AO_T1(3);
     }
-    slot = slot == 2 ? 0 : slot + 1;   // stage 4 (h + 1) = 4 h + 4 -> slot + 4 mod 3
+    slot = ao_slot_next(slot);   // stage 4 (h + 1) = 4 h + 4 -> slot + 4 mod 3
     // ---- Ba(h + 1): Q_h+1, K_h+1 landed (behind them: V_h+1  W_h,3  W_h+1,0  W_h+1,1); stage 3's slot -> W_h+1,2
-    ao_sync<4 * AO_UNIT, TM>(&tw[0], &tb[0]);
+    ao_sync<AO_WAIT_BA * AO_UNIT, TM>(&tw[0], &tb[0]);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) asm volatile("" : "+v"(qh[ks]), "+v"(ql[ks]));
-    if (h < 7) dma_w(4 * h + 6, slot == 0 ? 2 : slot - 1);
+    if (h < 7) dma_w(4 * h + 6, ao_slot_at(slot, 2));
     else dma_prow(1, 0, grpB0);
     AO_T0();
     if (h < 7) scores();
@@ -525,7 +526,7 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
           const int col = t * 32 + gq * 8;
           if (col + 8 <= ND) {
             const unsigned c = (unsigned)(tl * 8 + gq * 2) + (unsigned)g;
-            const float4 rsd = *reinterpret_cast<const float4*>(smem + (half == 0 ? rowA : rowB) + ((c ^ ((unsigned)m & 15u)) << 4));
+            const float4 rsd = *reinterpret_cast<const float4*>(smem + (half == 0 ? rowA : rowB) + (ao_row_chunk(c, (unsigned)m) << 4));
             const float4 b = *reinterpret_cast<const float4*>(bias + col);
             tile[gq * 4 + 0] = (tile[gq * 4 + 0] * a.out_scale + b.x) + rsd.x;
             tile[gq * 4 + 1] = (tile[gq * 4 + 1] * a.out_scale + b.y) + rsd.y;
@@ -623,9 +624,9 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
     {
       unsigned relW1[8], relW2[2];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) relW1[k] = m * RKB + ((((k << 1) | g) ^ (m & 15)) << 4);
+      for (int k = 0; k < 8; ++k) relW1[k] = ffn_w1_lane(m, g, k);
 #pragma unroll
-      for (int sx = 0; sx < 2; ++sx) relW2[sx] = m * 64 + (((2 * sx + g) ^ ((m >> 2) & 3)) << 4);
+      for (int sx = 0; sx < 2; ++sx) relW2[sx] = ffn_w2_lane(m, g, sx);
       const unsigned relB = lds0 + FB1_OFF + g * 16;
       FfnStream<29, AO_NT, 2, false, 6, true> F;
       F.xf = xf;
@@ -705,7 +706,7 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
           const int t = half * 8 + tl, col = t * 32 + gq * 8;
           if (col + 8 <= ND) {
             const unsigned c = (unsigned)(tl * 8 + gq * 2) + (unsigned)g;        // the lane's chunk of its row m
-            float4* pl = reinterpret_cast<float4*>(smem + (half == 0 ? rowA : rowB) + ((c ^ ((unsigned)m & 15u)) << 4));
+            float4* pl = reinterpret_cast<float4*>(smem + (half == 0 ? rowA : rowB) + (ao_row_chunk(c, (unsigned)m) << 4));
             const float4 rsd = *pl;
             const float4 b = *reinterpret_cast<const float4*>(bias + col);
             float4 y;
@@ -720,7 +721,7 @@ __global__ __launch_bounds__(256, 1) void attnout16x3_k(AttnOutArgs a) {
 #pragma unroll
       for (int r = 0; r < 32; ++r) {
         if (r < nrow) {
-          const unsigned lc = lu ^ (unsigned)(r & 15);
+          const unsigned lc = ao_row_chunk(lu, (unsigned)r);
           const unsigned base = half == 0 ? grpA[r >> 3] : (r < 8 ? grpB0 : grpA[(r >> 3) - 1]);
           const float4 y = *reinterpret_cast<const float4*>(smem + (base - lds0) + (r & 7) * 1024 + lu * 16u);
           if ((int)lc < nch)

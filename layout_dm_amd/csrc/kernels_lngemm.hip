@@ -32,40 +32,22 @@
 #include "ldm_dma.h"
 #include "ldm_kernels.h"
 #include "ldm_pipes.h"
+#include "ldm_x3_sched.h"
 
 namespace ldm {
 
+using namespace ldm_sched;
+
 namespace {
 
-// A tile is NIT = 30 queue items: the 29 k16-steps and ONE pseudo item (nothing is read, nothing is issued) so that
-// NIT % PF == 0 — item i of every tile then lives in queue slot i % PF and the queue runs on across tiles (FfnStream's trick;
-// r05's first GPU run had 29 items on the 6-deep queue: item 0 of the next tile landed in the slot of an unconsumed pair).
-// PF = 6 fragment pairs in flight.  Measured alternatives that did NOT ship (same-box A/B builds,
-// profiles/r05_call7_lngemm_queue_depth_and_agpr_accumulators_ab.txt): PF = 8 (32 items per tile) leaves 14 fragment reads
-// behind the awaited pair, the epilogue's LDS operations come on top and the 4-bit lgkmcnt counter no longer covers what is in
-// flight — NaN logits; the tile accumulators in AGPRs ("+a" MFMA destinations beside the AGPR-resident lo fragments) lose low-order
-// terms (logits error 5e-5 instead of 9e-7) and are not faster.
-constexpr int LG_KS = 29, LG_NIT = 30, LG_PF = 6, LG_SYNC = LG_NIT - LG_PF;
-static_assert(LG_NIT % LG_PF == 0, "queue slots must line up across tiles");
-constexpr bool lg_real(int i) { return (i % LG_NIT) < LG_KS; }
-// LDS reads issued behind the pair of item IT when step IT waits for it: the real items among IT + 1 .. IT + PF - 1
-// (rpi = LDS reads per item: W hi and W lo, or — W2, the two-product form: weights fp16 only — W hi alone)
-constexpr int lg_younger(int IT, int rpi = 2) {
-  int n = 0;
-  for (int j = 1; j < LG_PF; ++j) n += lg_real(IT + j) ? rpi : 0;
-  return n;
-}
-static_assert(lg_younger(0) <= 15, "lgkmcnt is a 4-bit counter");
-constexpr int LG_STAGE = 65536;                    // W hi tile (32 KiB) | W lo tile (32 KiB)
-constexpr int LG_LO = 32768;
-constexpr int LG_TP_LD = 36;                       // floats per row of a wave's 32 x 32 transpose buffer (16-B aligned rows)
-constexpr int LG_TP_BYTES = 32 * LG_TP_LD * 4;     // 4 608 B per wave
-constexpr int LG_PAR_OFF = 2 * LG_STAGE;           // multiplier [512] | shift [512]
-constexpr int LG_BIAS_OFF = LG_PAR_OFF + 2 * 512 * 4;   // bias [2048]
-constexpr int LG_TP_OFF = LG_BIAS_OFF + 2048 * 4;
-constexpr int LG_PBIAS_OFF = LG_TP_OFF + 4 * LG_TP_BYTES;   // bias of the GEMM prologue [512]
-constexpr int LG_LDS = LG_PBIAS_OFF + 512 * 4;              // 163 840 B = all of a CU's LDS
-static_assert(LG_LDS <= 160 * 1024, "LDS budget");
+// The schedule of the tile loop (LG: 30 queue items per tile — 29 k16-steps and one pseudo item —, 6 fragment pairs in flight), of
+// the GEMM prologue (LP) and the LDS map (LG_STAGE .. LG_LDS) are ldm_x3_sched.h's: the same header tests/cpu_x3_sched_check.cpp
+// dumps for the host replay (tests/test_lngemm_sched.py) and tests/test_kernel_asm_lint.py holds this file's ISA to.
+// (Another measured alternative that did not ship, profiles/r05_call7_lngemm_queue_depth_and_agpr_accumulators_ab.txt: the tile
+// accumulators in AGPRs — "+a" MFMA destinations beside the AGPR-resident lo fragments — lose low-order terms, logits error 5e-5
+// instead of 9e-7, and are not faster.)
+using LG = LgSched;
+using LP = LpSched;
 
 template <int OFF>
 __device__ __forceinline__ void lg_dsr(f16x8& d, unsigned addr) {
@@ -76,7 +58,7 @@ __device__ unsigned long long g_lngemm_phase[8];   // TM instantiation: workgrou
 
 struct LgState {
   unsigned long long t_sync = 0, t_lgkm = 0;   // (TM) cycles inside the per-tile vmcnt + barrier, inside the counted LDS waits
-  f16x8 qh[LG_PF], ql[LG_PF];   // W hi / lo fragment queue
+  f16x8 qh[LG::PF], ql[LG::PF];   // W hi / lo fragment queue
   unsigned aW[8];               // LDS byte addresses of the fragment columns in the CURRENT stage
   const f16x8* xhi;             // [29] activation fragments, hi (arch VGPRs)
   const f16x8* xlo;             // [29] ... lo (AGPRs)
@@ -94,16 +76,16 @@ struct LgState {
 // item IT of the tile whose stage aW points at: W hi and W lo fragment of k16-step IT (pseudo items: nothing)
 template <int IT, bool W2 = false>
 __device__ __forceinline__ void lg_read(LgState& s) {
-  if constexpr (IT < LG_KS) {
-    lg_dsr<256 * (IT >> 3)>(s.qh[IT % LG_PF], s.aW[IT & 7]);
-    if constexpr (!W2) lg_dsr<256 * (IT >> 3) + LG_LO>(s.ql[IT % LG_PF], s.aW[IT & 7]);
+  if constexpr (IT < LG::KS) {
+    lg_dsr<LG::read_off(IT)>(s.qh[IT % LG::PF], s.aW[LG::read_col(IT)]);
+    if constexpr (!W2) lg_dsr<LG::read_off(IT) + LG_LO>(s.ql[IT % LG::PF], s.aW[LG::read_col(IT)]);
   }
 }
 
 // the kernel prologue primes the queue: items 0 .. PF - 1 of tile 0
 template <int I, bool W2 = false>
 __device__ __forceinline__ void lg_prime(LgState& s) {
-  if constexpr (I < LG_PF) {
+  if constexpr (I < LG::PF) {
     lg_read<I, W2>(s);
     lg_prime<I + 1, W2>(s);
   }
@@ -153,7 +135,8 @@ struct LgEpi {
 static_assert(kSplitLoScale == 1.0f, "the lo half is stored unscaled");
 // chain A + chain B -> the wave's transpose buffer (the exposed part)
 __device__ __forceinline__ void lg_epilogue_sum_write(const LgEpi& e, f32x16& a, f32x16& b) {
-  wait_lgkm<8>();   // (4 ds_write_b128 follow: lgkmcnt is a 4-bit counter)
+  static_assert(LG::EPI_WRITES == 4, "the four ds_write_b128 below");
+  wait_lgkm<LG::EPI_DRAIN>();   // (EPI_WRITES ds_write_b128 follow: lgkmcnt is a 4-bit counter)
   asm volatile("s_nop 15\n\ts_nop 15" : "+v"(a), "+v"(b));   // the chains' last MFMAs (8 passes each): results visible to the VALU
 #pragma unroll
   for (int rq = 0; rq < 4; ++rq) {
@@ -167,7 +150,7 @@ __device__ __forceinline__ void lg_epilogue_sum_write(const LgEpi& e, f32x16& a,
 }
 template <int IT, int OUT, int ABL = 0>
 __device__ __forceinline__ void lg_epilogue_slice(LgEpi& e, int tile) {
-  if constexpr (IT == 1) {
+  if constexpr (LG::epi_bias_step(IT)) {
     const unsigned ab = e.a_bias + (unsigned)tile * 128;
     asm volatile("ds_read_b128 %0, %1" : "=v"(e.bb) : "v"(ab) : "memory");
     // (tile == -1, the slices of the first tile's steps: an unsigned compare masks every lane — the passes run and store nothing)
@@ -176,13 +159,13 @@ __device__ __forceinline__ void lg_epilogue_slice(LgEpi& e, int tile) {
     e.b0 = e.C0 + ((ABL & 32) ? 0 : (size_t)tile * e.tstride);
     e.b1 = e.C1 + ((ABL & 32) ? 0 : (size_t)tile * e.tstride);
   }
-  if constexpr (IT == 2 || IT == 3) {
-    constexpr int p0 = (IT - 2) * 2;
+  if constexpr (LG::epi_readback_step(IT)) {
+    constexpr int p0 = LG::epi_readback_pass(IT);
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(e.ev[p0]) : "v"(e.a_tpr), "n"(p0 * 8 * LG_TP_LD * 4) : "memory");
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(e.ev[p0 + 1]) : "v"(e.a_tpr), "n"((p0 + 1) * 8 * LG_TP_LD * 4) : "memory");
   }
-  if constexpr (IT > LG_SYNC && IT <= LG_SYNC + 4) {
-    constexpr int p = IT - LG_SYNC - 1;
+  if constexpr (LG::epi_store_step(IT)) {
+    constexpr int p = LG::epi_store_pass(IT);
     const lg_f32x4 ev = e.ev[p];
     float t0, t1, t2, t3;
     if constexpr (OUT == 0) {
@@ -251,9 +234,6 @@ __device__ __forceinline__ void lg_epilogue_slice(LgEpi& e, int tile) {
     }
   }
 }
-constexpr bool lg_slice_step(int IT) {
-  return IT == 1 || IT == 2 || IT == 3 || (IT > LG_SYNC && IT <= LG_SYNC + 4);
-}
 
 // One tile = NIT steps.  A real step (a k16-step) is ONE asm statement: the counted wait, then its three MFMAs with the step's
 // LDS-DMA piece and its two fragment reads BETWEEN them:
@@ -316,14 +296,7 @@ constexpr bool lg_slice_step(int IT) {
 #define LG_A_RDL "ds_read_b128 %[ql], %[aw] offset:%[rl]"
 #define LG_A_RDH2 "ds_read_b128 %[qh], %[aw] offset:%[ro]"
 
-// which DMA piece (of the 16 per tile and wave) step IT carries, or -1: pieces 0 .. NIT - 2 - SYNC of tile + 2 at steps SYNC + 1 ..
-// NIT - 1 (its stage — this tile's — is free behind this tile's barrier), the rest at the first steps of the next tile
-constexpr int lg_piece(int IT) {
-  if (IT > LG_SYNC) return IT - LG_SYNC - 1;
-  if (IT + (LG_NIT - 1 - LG_SYNC) < 16) return IT + (LG_NIT - 1 - LG_SYNC);
-  return -1;
-}
-static_assert(lg_piece(LG_SYNC) == -1 && lg_piece(LG_SYNC + 1) == 0 && lg_piece(0) == lg_piece(LG_NIT - 1) + 1, "16 pieces, in order, none at the barrier step");
+static_assert(LG::piece(LG::SYNC) == -1 && LG::piece(LG::SYNC + 1) == 0 && LG::piece(0) == LG::piece(LG::NIT - 1) + 1, "16 pieces, in order, none at the barrier step");
 
 template <int IT, int OUT, bool TM = false, int ABL = 0, int NP = 3>   // NP products per k16-step: 3 | 2 (weights fp16 only) | 1 (plain fp16: x_hi too)
 __device__ __forceinline__ void lg_step(LgState& s, LgEpi& e, int tile) {
@@ -332,28 +305,27 @@ __device__ __forceinline__ void lg_step(LgState& s, LgEpi& e, int tile) {
   // 4 = the weight DMA, 8 = the epilogue (sum, transpose, stores), 16 = the epilogue's global stores only, 32 = every tile's stores
   // aimed at the columns of tile 0 — timing variants of this loop, results meaningless
   constexpr bool kRd = !(ABL & 2), kDm = !(ABL & 4), kEp = !(ABL & 8);
-  if constexpr (IT < LG_NIT) {
-    constexpr int J = lg_piece(IT);
-    constexpr bool hasD = kDm && J >= 0 && (!W2 || J < 8);   // (W2: only the stage's hi half is fetched — 8 KiB per wave, pieces 0 .. 7)
+  if constexpr (IT < LG::NIT) {
+    constexpr bool hasD = kDm && LG::has_dma(IT, NP);   // (W2: only the stage's hi half is fetched — 8 KiB per wave, pieces 0 .. 7)
     // the DMA stream's uniform address state: a new tile at piece 0, the next 4-KiB group of this wave's 16 KiB at pieces 4, 8, 12
-    if constexpr (hasD && J == 0) lg_dma_begin(s, tile + 2);
-    if constexpr (hasD && J > 0 && (J & 3) == 0) {
+    if constexpr (kDm && LG::dma_begin(IT, NP)) lg_dma_begin(s, tile + 2);
+    if constexpr (kDm && LG::dma_advance(IT, NP)) {
       s.dma_g += 4096;
       s.dma_l += 4096;
     }
     // the fragment pair PF items ahead (pseudo items: nothing); the one behind the barrier step is read behind the barrier
-    constexpr int RI = (IT + LG_PF) % LG_NIT;
-    constexpr bool hasR = kRd && IT != LG_SYNC && RI < LG_KS;
-    constexpr int RO = 256 * (RI >> 3);
-    constexpr int DOFF = hasD ? (J & 3) * 1024 : 0;
-    if constexpr (IT < LG_KS) {
-      // LDS operations of a wave complete in order: all but the lg_younger(IT) youngest = the fragment pairs issued behind item IT's
-      constexpr int W = kRd ? lg_younger(IT, W2 ? 1 : 2) : 15;
+    constexpr int RI = LG::read_item(IT);
+    constexpr bool hasR = kRd && LG::reads(IT);
+    constexpr int RO = LG::read_off(RI);
+    constexpr int DOFF = kDm ? LG::dma_off(IT, NP) : 0;
+    if constexpr (IT < LG::KS) {
+      // LDS operations of a wave complete in order: all but the LG::wait youngest = the fragment pairs issued behind item IT's
+      constexpr int W = kRd ? LG::wait(IT, NP) : 15;
       f32x16& c0 = ((IT & 1) && NP != 2) ? s.accB : s.accA;   // two of the step's MFMAs (NP = 2: one; NP = 1: the step's only one)
       f32x16& c1 = ((IT & 1) && NP != 2) ? s.accA : s.accB;   // one (NP = 1: unused)
-      f16x8& qh = s.qh[IT % LG_PF];
-      f16x8& ql = s.ql[IT % LG_PF];
-      const unsigned aw = s.aW[RI & 7];
+      f16x8& qh = s.qh[IT % LG::PF];
+      f16x8& ql = s.ql[IT % LG::PF];
+      const unsigned aw = s.aW[LG::read_col(RI)];
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (NP == 1 && IT < 2) {   // one product: step 0 starts chain A, step 1 chain B
         if constexpr (hasD && hasR) LG_STEP_ASM1("0", LG_A_M0, LG_A_PIECE, LG_A_RDH2);
@@ -395,14 +367,14 @@ __device__ __forceinline__ void lg_step(LgState& s, LgEpi& e, int tile) {
         dma_lin<DOFF>(s.voff, s.dma_g);
       }
     }
-    if constexpr (IT == LG_SYNC - 1) {
+    if constexpr (IT == LG::FLIP) {
       // item NIT - 1 (the last item of this tile) has just been issued: aW now points into the next tile's stage
 #pragma unroll
       for (int k = 0; k < 8; ++k) s.aW[k] += (unsigned)s.stage_delta;
       s.stage_delta = -s.stage_delta;
     }
     // ---- the per-tile barrier ...
-    if constexpr (IT == LG_SYNC) {
+    if constexpr (IT == LG::SYNC) {
       // the next tile's stage is complete (own DMA pieces landed, then everybody's), and every wave has ISSUED all its reads of
       // this tile (the last real one at step KS - 1 - PF): this tile's stage may be overwritten from here on
       unsigned long long tw = 0;
@@ -412,12 +384,12 @@ __device__ __forceinline__ void lg_step(LgState& s, LgEpi& e, int tile) {
       asm volatile("" ::: "memory");
       if constexpr (TM) s.t_sync += __builtin_amdgcn_s_memtime() - tw;
       // (the next tile's item 0 is read only now, behind the barrier)
-      if constexpr (kRd) lg_read<RI, W2>(s);
+      if constexpr (kRd && LG::reads_behind_barrier(IT)) lg_read<RI, W2>(s);
     }
     // ---- ... and a slice of the previous tile's epilogue
-    if constexpr (kEp && lg_slice_step(IT)) lg_epilogue_slice<IT, OUT, ABL>(e, tile - 1);
+    if constexpr (kEp && LG::slice_step(IT)) lg_epilogue_slice<IT, OUT, ABL>(e, tile - 1);
     // ---- the pseudo step: the tile's sum goes to the transpose buffer (the previous tile's rows left it at steps 2, 3)
-    if constexpr (kEp && IT == LG_KS) lg_epilogue_sum_write(e, s.accA, s.accB);
+    if constexpr (kEp && IT == LG::KS) lg_epilogue_sum_write(e, s.accA, s.accB);
     __builtin_amdgcn_sched_barrier(0);
     lg_step<IT + 1, OUT, TM, ABL, NP>(s, e, tile);
   }
@@ -439,21 +411,11 @@ __device__ __forceinline__ void lg_step(LgState& s, LgEpi& e, int tile) {
 // counted vmcnt leaves the youngest four of them in flight).
 // Per workgroup: K / 32 stages x 64 KiB of weight slabs (linear2: 58 stages = 3.7 MB, the
 // same bytes gemm16x3_k's 256 x 256 tile pulls for BOTH operands) and no launch, no fp32 round trip of the sum, no epilogue.
-constexpr int LP_NT = 15, LP_NIT = 2 * LP_NT;   // items per stage
-// a 3-deep fragment queue (the tile loop: 6): 24 registers — what it saves holds the third A register set, which hides the HBM latency of
-// the A rows (22 - 27 us per launch, measurement variant 128); 3 items ahead are ~300 cycles of MFMA time, the LDS answers in ~130
-constexpr int LP_PF = 3, LP_SYNC = LP_NIT - LP_PF;
-static_assert(LP_NIT % LP_PF == 0, "queue slots must line up across stages");
-// which of the 16 DMA pieces per wave and stage step IT carries: pieces 0 .. behind the barrier, the rest at the first steps of the next stage
-constexpr int lp_piece(int IT) {
-  if (IT > LP_SYNC) return IT - LP_SYNC - 1;
-  if (IT + (LP_NIT - 1 - LP_SYNC) < 16) return IT + (LP_NIT - 1 - LP_SYNC);
-  return -1;
-}
-static_assert(lp_piece(LP_SYNC) == -1 && lp_piece(LP_SYNC + 1) == 0 && lp_piece(0) == lp_piece(LP_NIT - 1) + 1, "16 pieces, in order, none at the barrier step");
+// (LP, ldm_x3_sched.h: 30 items per stage, a 3-deep fragment queue — the A loads of stage + 2 hide behind what it saves in registers)
+static_assert(LP::piece(LP::SYNC) == -1 && LP::piece(LP::SYNC + 1) == 0 && LP::piece(0) == LP::piece(LP::NIT - 1) + 1, "16 pieces, in order, none at the barrier step");
 
 struct LpState {
-  f16x8 qh[LP_PF], ql[LP_PF];   // W hi / lo fragment queue
+  f16x8 qh[LP::PF], ql[LP::PF];   // W hi / lo fragment queue
   unsigned aS[2];               // this lane's LDS address of k16-step s in the CURRENT stage (tile t: + t * 2 KiB)
   f16x8 fh[3][2], fl[3][2];     // A fragments [stage % 3][k16-step]: the current stage's, the next stage's (landed by the current
                                 // stage's barrier) and the one after's (requested in this stage, in flight across its barrier: the
@@ -472,13 +434,12 @@ struct LpState {
 
 template <int IT, bool W2 = false>
 __device__ __forceinline__ void lp_read(LpState& s) {   // item IT of the stage aS points at
-  constexpr int sx = IT / LP_NT, t = IT % LP_NT;
-  lg_dsr<t * 2048>(s.qh[IT % LP_PF], s.aS[sx]);
-  if constexpr (!W2) lg_dsr<t * 2048 + LG_LO>(s.ql[IT % LP_PF], s.aS[sx]);
+  lg_dsr<LP::read_off(IT)>(s.qh[IT % LP::PF], s.aS[LP::read_reg(IT)]);
+  if constexpr (!W2) lg_dsr<LP::read_off(IT) + LG_LO>(s.ql[IT % LP::PF], s.aS[LP::read_reg(IT)]);
 }
 template <int I, bool W2 = false>
 __device__ __forceinline__ void lp_prime(LpState& s) {
-  if constexpr (I < LP_PF) {
+  if constexpr (I < LP::PF) {
     lp_read<I, W2>(s);
     lp_prime<I + 1, W2>(s);
   }
@@ -488,9 +449,9 @@ __device__ __forceinline__ void lp_dma_begin(LpState& s, int sd) {   // stage sd
   s.dma_g = s.img + (size_t)t * LG_STAGE;
   s.dma_l = s.lds_w + (unsigned)(sd & 1) * LG_STAGE;
 }
-// A fragments of stage sd (clamped) into register set P: k16-steps 2 sd, 2 sd + 1 -> 16 halves apart.  EXACTLY LP_A_LOADS vector
-// memory instructions: the stage barrier's counted wait leaves that many outstanding.
-constexpr int LP_A_LOADS = 4;   // (HI_ONLY — the one-product form, A is plain fp16: LP_A_LOADS / 2)
+// A fragments of stage sd (clamped) into register set P: k16-steps 2 sd, 2 sd + 1 -> 16 halves apart.  EXACTLY LP::a_loads vector
+// memory instructions (HI_ONLY — the one-product form, A is plain fp16: half as many): the stage barrier's counted wait leaves that
+// many outstanding.
 template <int P, bool HI_ONLY = false>
 __device__ __forceinline__ void lp_load_a(LpState& s, int sd) {
 #ifdef LDM_LNGEMM_ABL_BUILD   // measurement build, LDM_LNGEMM_ABL=128: every stage re-reads the A fragments of stage 0 (L2-resident)
@@ -511,78 +472,73 @@ __device__ __forceinline__ void lp_load_a(LpState& s, int sd) {
                    PIECE RD_HI RD_LO TAIL                                                                                          \
                : [c] "+a"(acc), [qh] "+v"(qh), [ql] "+v"(ql)                                                                       \
                : [xh] "v"(s.fh[SET][sx]), [xl] "v"(s.fl[SET][sx]), [aw] "v"(aw), [vo] "v"(s.voff), [dg] "s"(s.dma_g), [dl] "s"(s.dma_l),     \
-                 [w] "n"(2 * (LP_PF - 1)), [ro] "n"(RO), [rl] "n"(RO + LG_LO), [doff] "n"(DOFF)                                    \
+                 [w] "n"(LP::wait(NP)), [ro] "n"(RO), [rl] "n"(RO + LG_LO), [doff] "n"(DOFF)                                    \
                : "memory")
 #define LP_STEP_ASM2(M0SET, PIECE, RD_HI, TAIL)   /* W2: W_hi a_hi + W_hi a_lo */                                                 \
   asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" M0SET LP_MFMA("%[qh]", "%[xh]") LP_MFMA("%[qh]", "%[xl]") PIECE RD_HI TAIL            \
                : [c] "+a"(acc), [qh] "+v"(qh)                                                                                      \
                : [xh] "v"(s.fh[SET][sx]), [xl] "v"(s.fl[SET][sx]), [aw] "v"(aw), [vo] "v"(s.voff), [dg] "s"(s.dma_g), [dl] "s"(s.dma_l),     \
-                 [w] "n"(LP_PF - 1), [ro] "n"(RO), [doff] "n"(DOFF)                                                                \
+                 [w] "n"(LP::wait(NP)), [ro] "n"(RO), [doff] "n"(DOFF)                                                                \
                : "memory")
 #define LP_STEP_ASM1(M0SET, PIECE, RD_HI, TAIL)   /* one product: W_hi a_hi */                                                   \
   asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" M0SET LP_MFMA("%[qh]", "%[xh]") PIECE RD_HI TAIL                                    \
                : [c] "+a"(acc), [qh] "+v"(qh)                                                                                      \
                : [xh] "v"(s.fh[SET][sx]), [aw] "v"(aw), [vo] "v"(s.voff), [dg] "s"(s.dma_g), [dl] "s"(s.dma_l),                     \
-                 [w] "n"(LP_PF - 1), [ro] "n"(RO), [doff] "n"(DOFF)                                                                \
+                 [w] "n"(LP::wait(NP)), [ro] "n"(RO), [doff] "n"(DOFF)                                                                \
                : "memory")
-
-// the step at which the stage requests the A fragments of stage + 2: behind the last DMA piece of the slab the barrier certifies
-constexpr int LP_A_STEP = 15;
-static_assert(lp_piece(LP_A_STEP - 1) < 0 && lp_piece(LP_A_STEP) < 0 && LP_A_STEP < LP_SYNC, "A loads are the youngest vector memory operations at the barrier");
 
 template <int IT, int SET, int NP = 3>   // SET = stage % 3: the A register set the stage multiplies; NP products per item (1: A hi only, plain fp16)
 __device__ __forceinline__ void lp_step(LpState& s, f32x16* accs, int stage) {
   constexpr bool W2 = NP < 3;
-  if constexpr (IT < LP_NIT) {
-    constexpr int sx = IT / LP_NT, t = IT % LP_NT;
-    constexpr int J = lp_piece(IT);
-    constexpr bool hasD = J >= 0 && (!W2 || J < 8);   // (W2: the slab's hi half only)
-    if constexpr (hasD && J == 0) lp_dma_begin(s, stage + 2);
-    if constexpr (hasD && J > 0 && (J & 3) == 0) {
+  if constexpr (IT < LP::NIT) {
+    constexpr int sx = LP::kstep(IT), t = LP::tile(IT);   // the item: k16-step sx of the slab, tile t
+    constexpr bool hasD = LP::has_dma(IT, NP);   // (W2: the slab's hi half only)
+    if constexpr (LP::dma_begin(IT, NP)) lp_dma_begin(s, stage + 2);
+    if constexpr (LP::dma_advance(IT, NP)) {
       s.dma_g += 4096;
       s.dma_l += 4096;
     }
-    // the A fragments of stage + 2: requested behind this stage's last DMA piece, so that they are the LP_A_LOADS youngest vector
+    // the A fragments of stage + 2: requested behind this stage's last DMA piece, so that they are the LP::a_loads youngest vector
     // memory operations at the barrier, which does not wait for them (loads return in order: everything older has landed)
-    if constexpr (IT == LP_A_STEP) lp_load_a<(SET + 2) % 3, NP == 1>(s, stage + 2);
-    constexpr int RI = (IT + LP_PF) % LP_NIT;
-    constexpr bool hasR = IT != LP_SYNC;
-    constexpr int RO = (RI % LP_NT) * 2048;
-    constexpr int DOFF = hasD ? (J & 3) * 1024 : 0;
+    if constexpr (IT == LP::A_STEP) lp_load_a<(SET + 2) % 3, NP == 1>(s, stage + 2);
+    constexpr int RI = LP::read_item(IT);
+    constexpr bool hasR = LP::reads(IT);
+    constexpr int RO = LP::read_off(RI);
+    constexpr int DOFF = LP::dma_off(IT, NP);
     f32x16& acc = accs[t];
-    f16x8& qh = s.qh[IT % LP_PF];
-    f16x8& ql = s.ql[IT % LP_PF];
-    const unsigned aw = s.aS[RI / LP_NT];
+    f16x8& qh = s.qh[IT % LP::PF];
+    f16x8& ql = s.ql[IT % LP::PF];
+    const unsigned aw = s.aS[LP::read_reg(RI)];
     __builtin_amdgcn_sched_barrier(0);
     // the stage's last item: 32 wait states behind its MFMAs, inside the statement (whatever hipcc places behind the stage loop —
     // its v_accvgpr_reads of the tiles — then finds every MFMA of the phase finished)
-    static_assert(lp_piece(LP_NIT - 1) >= 0 && LP_NIT - 1 != LP_SYNC, "the last item carries a DMA piece and its reads");
+    static_assert(LP::has_dma(LP::NIT - 1, 1) && LP::reads(LP::NIT - 1), "the last item carries a DMA piece and its reads");
     if constexpr (NP == 1) {
-      if constexpr (IT == LP_NIT - 1) LP_STEP_ASM1(LG_A_M0, LG_A_PIECE, LG_A_RDH2 "\n\t", "s_nop 15\n\ts_nop 15");
+      if constexpr (IT == LP::NIT - 1) LP_STEP_ASM1(LG_A_M0, LG_A_PIECE, LG_A_RDH2 "\n\t", "s_nop 15\n\ts_nop 15");
       else if constexpr (hasD && hasR) LP_STEP_ASM1(LG_A_M0, LG_A_PIECE, LG_A_RDH2, "");
       else if constexpr (hasD) LP_STEP_ASM1(LG_A_M0, LG_A_PIECE, "", "");
       else if constexpr (hasR) LP_STEP_ASM1("", "", LG_A_RDH2, "");
       else LP_STEP_ASM1("", "", "", "");
     } else if constexpr (W2) {
-      if constexpr (IT == LP_NIT - 1) LP_STEP_ASM2(LG_A_M0, LG_A_PIECE, LG_A_RDH2 "\n\t", "s_nop 15\n\ts_nop 15");
+      if constexpr (IT == LP::NIT - 1) LP_STEP_ASM2(LG_A_M0, LG_A_PIECE, LG_A_RDH2 "\n\t", "s_nop 15\n\ts_nop 15");
       else if constexpr (hasD && hasR) LP_STEP_ASM2(LG_A_M0, LG_A_PIECE, LG_A_RDH2, "");
       else if constexpr (hasD) LP_STEP_ASM2(LG_A_M0, LG_A_PIECE, "", "");
       else if constexpr (hasR) LP_STEP_ASM2("", "", LG_A_RDH2, "");
       else LP_STEP_ASM2("", "", "", "");
-    } else if constexpr (IT == LP_NIT - 1) LP_STEP_ASM(LG_A_M0, LG_A_PIECE, LG_A_RDH, LG_A_RDL "\n\t", "s_nop 15\n\ts_nop 15");
+    } else if constexpr (IT == LP::NIT - 1) LP_STEP_ASM(LG_A_M0, LG_A_PIECE, LG_A_RDH, LG_A_RDL "\n\t", "s_nop 15\n\ts_nop 15");
     else if constexpr (hasD && hasR) LP_STEP_ASM(LG_A_M0, LG_A_PIECE, LG_A_RDH, LG_A_RDL, "");
     else if constexpr (hasD) LP_STEP_ASM(LG_A_M0, LG_A_PIECE, "", "", "");
     else if constexpr (hasR) LP_STEP_ASM("", "", LG_A_RDH, LG_A_RDL, "");
     else LP_STEP_ASM("", "", "", "", "");
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (IT == LP_SYNC - 1) {   // the stage's last item has been requested: aS moves to the next stage's slot
+    if constexpr (IT == LP::FLIP) {   // the stage's last item has been requested: aS moves to the next stage's slot
       s.aS[0] += (unsigned)s.stage_delta;
       s.aS[1] += (unsigned)s.stage_delta;
       s.stage_delta = -s.stage_delta;
     }
-    if constexpr (IT == LP_SYNC) {
+    if constexpr (IT == LP::SYNC) {
       // the next stage's slab (own pieces) and its A fragments (requested a stage ago); the fragments of stage + 2 stay in flight
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NP == 1 ? LP_A_LOADS / 2 : LP_A_LOADS) : "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LP::a_loads(NP)) : "memory");
       __builtin_amdgcn_s_barrier();
       if constexpr (NP == 1) asm volatile("" : "+v"(s.fh[(SET + 1) % 3][0]), "+v"(s.fh[(SET + 1) % 3][1])::"memory");
       else asm volatile("" : "+v"(s.fh[(SET + 1) % 3][0]), "+v"(s.fh[(SET + 1) % 3][1]), "+v"(s.fl[(SET + 1) % 3][0]), "+v"(s.fl[(SET + 1) % 3][1])::"memory");   // (hipcc's own counted wait for them lands here)
@@ -626,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   const int rrow = row < a.M ? row : a.M - 1;
 
   // ---- GEMM prologue: the rows are computed here instead of read (out_proj / linear2 in front of the LayerNorm that takes their sum)
-  f32x16 pacc[PRE ? LP_NT : 1];
+  f32x16 pacc[PRE ? LP::NT : 1];
   if constexpr (PRE) {
     float* spb = reinterpret_cast<float*>(smem + LG_PBIAS_OFF);
     for (int i = tid; i < 512; i += 256) spb[i] = (a.pre_bias && i < a.D) ? a.pre_bias[i] : 0.f;
@@ -656,12 +612,12 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
 #pragma unroll
     for (int sx = 0; sx < 2; ++sx) ps.aS[sx] = lds0 + r * 64 + ((((sx << 1) | hi) ^ ((r >> 2) & 3)) << 4);
 #pragma unroll
-    for (int t = 0; t < LP_NT; ++t)
+    for (int t = 0; t < LP::NT; ++t)
 #pragma unroll
       for (int k = 0; k < 16; ++k) pacc[t][k] = 0.f;
     lp_dma_begin(ps, 1);
     {  // (stage 0, steps 0 ..: the pieces of slab 1 once more, as in the tile loop)
-      constexpr int J0 = lp_piece(0), pre = (J0 >> 2) - ((J0 & 3) == 0 ? 1 : 0);
+      constexpr int pre = LP::first_group();
       ps.dma_g += pre * 4096;
       ps.dma_l += pre * 4096;
     }
@@ -744,10 +700,10 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   __syncthreads();  // parameter tables visible
   // normalise, write the residual base (ADA), split into hi / lo fragments: groups 2 ks, 2 ks + 1 -> fragment ks.  The hi
   // fragment takes the place of the raw values it was made from (v[] dies pair by pair), the lo fragment goes to AGPRs.
-  f16x8 xhi[LG_KS], xlo[LG_KS];
+  f16x8 xhi[LG::KS], xlo[LG::KS];
   float* yrow = (ADA && a.y32) ? a.y32 + (size_t)rrow * a.D + hi * 4 : nullptr;
 #pragma unroll
-  for (int ks = 0; ks < LG_KS; ++ks) {
+  for (int ks = 0; ks < LG::KS; ++ks) {
     f16x8 fh, fl;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -788,7 +744,7 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   s.dma_g = img;   // (tile 0, steps 0 .. : the pieces of "tile 1" once more — what the prologue's DMA already brings)
   lg_dma_begin(s, 1);
   {  // the 4-KiB group of the first piece issued at step 0 (lg_step itself moves on at pieces 4, 8, 12)
-    constexpr int J0 = lg_piece(0), pre = (J0 >> 2) - ((J0 & 3) == 0 ? 1 : 0);
+    constexpr int pre = LG::first_group();
     s.dma_g += pre * 4096;
     s.dma_l += pre * 4096;
   }
@@ -817,7 +773,7 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   }
   // every fragment back in its registers, hipcc's scoreboard drained (its own row loads / y32 stores), tiles 0 / 1 landed
 #pragma unroll
-  for (int k = 0; k < LG_KS; ++k) {
+  for (int k = 0; k < LG::KS; ++k) {
     if constexpr (NPM > 1) asm volatile("" : "+v"(xhi[k]), "+a"(xlo[k]));
     else if (k & 1) asm volatile("" : "+a"(xhi[k]));
     else asm volatile("" : "+v"(xhi[k]));
@@ -831,7 +787,7 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   if constexpr (TM) t_pro = __builtin_amdgcn_s_memtime();
   if constexpr (ABL != 0) {   // (timing variants: whatever they leave unwritten starts defined)
     for (int k = 0; k < 16; ++k) s.accA[k] = s.accB[k] = 0.f;
-    for (int k = 0; k < LG_PF; ++k) s.qh[k] = s.ql[k] = xhi[k];
+    for (int k = 0; k < LG::PF; ++k) s.qh[k] = s.ql[k] = xhi[k];
   }
   if constexpr (!(ABL & 2)) lg_prime<0, W2>(s);
   for (int t = 0; t < a.n_tiles; ++t) lg_step<0, OUT, TM, ABL, NPM>(s, e, t);
@@ -841,10 +797,10 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   lg_epilogue_slice<2, OUT>(e, a.n_tiles - 1);
   lg_epilogue_slice<3, OUT>(e, a.n_tiles - 1);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  lg_epilogue_slice<LG_SYNC + 1, OUT>(e, a.n_tiles - 1);
-  lg_epilogue_slice<LG_SYNC + 2, OUT>(e, a.n_tiles - 1);
-  lg_epilogue_slice<LG_SYNC + 3, OUT>(e, a.n_tiles - 1);
-  lg_epilogue_slice<LG_SYNC + 4, OUT>(e, a.n_tiles - 1);
+  lg_epilogue_slice<LG::SYNC + 1, OUT>(e, a.n_tiles - 1);
+  lg_epilogue_slice<LG::SYNC + 2, OUT>(e, a.n_tiles - 1);
+  lg_epilogue_slice<LG::SYNC + 3, OUT>(e, a.n_tiles - 1);
+  lg_epilogue_slice<LG::SYNC + 4, OUT>(e, a.n_tiles - 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if constexpr (TM) {
     const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -889,7 +845,7 @@ int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st) {
   const bool tm = knob_int("LDM_LNGEMM_TM", 0) != 0;   // (dev: the phase-timer instantiation, tools/lngemm_probe.py; read per launch: cheap, dev mode only)
   const bool pre = a.pre_img != nullptr;
   // GEMM prologue: a multiple of three 32-wide K slabs (zero slabs behind the pre_astages real ones), all d_model columns inside its 15 tiles, fp32 residual rows
-  if (pre && (a.pre_stages < 3 || a.pre_stages % 3 || a.pre_astages < 2 || a.pre_astages > a.pre_stages || a.D > 32 * LP_NT || !a.preA ||
+  if (pre && (a.pre_stages < 3 || a.pre_stages % 3 || a.pre_astages < 2 || a.pre_astages > a.pre_stages || a.D > 32 * LP::NT || !a.preA ||
               (!a.preAlo && npp != 1) || !a.pre_res || a.tokens ||
               (a.pre_panel_stride ? ((a.pre_panel_stride & 15) || a.pre_panel_stride < (size_t)a.M * 64) : (a.pre_lda < 32 * a.pre_astages || (a.pre_lda & 7)))))
     return -1;

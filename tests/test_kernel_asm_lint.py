@@ -15,6 +15,8 @@ import subprocess
 
 import pytest
 
+import _x3_sched as x3
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 VALU_TO_MFMA_WAIT_STATES = 4
@@ -53,6 +55,43 @@ def _kernels(asm: str):
             continue
         cur.append(("asm:" if in_asm else "") + t.split(";")[0].strip())
     return out
+
+
+def _asm_statements(asm: str):
+    """name -> the inline-asm statements of every kernel in program order, one list of instructions per ;;#ASMSTART / ;;#ASMEND pair."""
+    names = set(re.findall(r"\.amdhsa_kernel\s+(\S+)", asm))
+    out, cur, stmt = {}, None, None
+    for line in asm.splitlines():
+        t = line.strip()
+        m = re.match(r"^(\S+):\s*(;.*)?$", t)
+        if m and m.group(1) in names:
+            cur = out.setdefault(m.group(1), [])
+        elif t.startswith(".Lfunc_end"):
+            cur = None
+        elif cur is not None and t.startswith(";;#ASMSTART"):
+            stmt = []
+        elif cur is not None and t.startswith(";;#ASMEND"):
+            cur.append(stmt)
+            stmt = None
+        elif stmt is not None and t and t[0] not in ";.":
+            stmt.append(t.split(";")[0].strip())
+    return out
+
+
+def _steps_follow_the_schedule(name, steps, table, n_products, lo):
+    """One inline-asm statement per step of a hand-issued weight stream (kernels_lngemm.hip LG_STEP_ASM / LP_STEP_ASM) against the
+    step's row of the schedule table (csrc/ldm_x3_sched.h through tests/cpu_x3_sched_check.cpp): the counted wait that opens it, its
+    DMA piece and the piece's offset immediate, its fragment reads' offset immediates (W hi; with three products W lo at + lo)."""
+    assert len(steps) == len(table), (name, len(steps), len(table))
+    off = lambda ins: int(re.search(r"offset:(\w+)", ins).group(1), 0)
+    for st, r in zip(steps, table):
+        where = (name, r["it"], st)
+        assert sum(i.startswith("v_mfma") for i in st) == n_products, where
+        assert st[0] == f"s_waitcnt lgkmcnt({r['wait']})", where
+        assert [off(i) for i in st if i.startswith("global_load_lds_dwordx4")] == ([r["doff"]] if r["dma"] else []), where
+        assert sum(i.startswith("s_mov_b32 m0") for i in st) == r["dma"], where
+        want = ([r["roff"]] + ([r["roff"] + lo] if n_products == 3 else [])) if r["read"] else []
+        assert [off(i) for i in st if i.startswith("ds_read_b128")] == want, where
 
 
 def _regs(tok: str):
@@ -209,6 +248,7 @@ def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards(tmp_path):
     assert {tuple(int(x) for x in FORM.search(k).groups()) for k in kernels} == reachable, list(_kernels(asm))
     assert len(kernels) == 14
     sizes = dict(re.findall(r"\.amdhsa_kernel\s+(\S+)[\s\S]*?\.amdhsa_private_segment_fixed_size\s+(\d+)", asm))
+    statements = _asm_statements(asm)
     for name, instr in kernels.items():
         assert int(sizes[name]) == 0 and not [i for i in instr if i.startswith("scratch_")], name
         mf = [i for i, t in enumerate(instr) if t.startswith("asm:v_mfma")]
@@ -216,6 +256,15 @@ def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards(tmp_path):
         pre, per, ppre = m.group(1) == "1", int(m.group(2)), int(m.group(3))   # products per k16-step: tile loop / GEMM prologue
         # tile body: 29 k16-steps x per products; the GEMM prologue adds three stage bodies (one per A register set) of 30 items x ppre
         assert len(mf) == per * 29 + (ppre * 90 if pre else 0), (name, len(mf))
+        # the binary follows the header the host replays (tests/test_lngemm_sched.py): every step statement — a counted LDS wait, then
+        # MFMAs — against its row of the schedule table.  The tile body's 29 steps come last, the prologue's first stage body first.
+        steps = [s for s in statements[name] if s and s[0].startswith("s_waitcnt lgkmcnt(") and any(i.startswith("v_mfma") for i in s)]
+        lo = x3.row("lg_lds")["LO"]
+        _steps_follow_the_schedule(name, steps[-29:], x3.rows("lg", np=per, real=1), per, lo)
+        if pre:
+            assert len(steps) == 29 + 90, (name, len(steps))
+            for body in range(3):   # (one stage body per A register set)
+                _steps_follow_the_schedule(name, steps[30 * body:30 * body + 30], x3.rows("lp", np=ppre), ppre, lo)
         if pre:
             # the matrix pipe runs its queue in order: the last stage's final MFMAs are still in flight when the stage loop falls through, and
             # hipcc (which cannot see asm MFMAs) puts its v_accvgpr_reads of the accumulator tiles right there — the wait states must sit inside
