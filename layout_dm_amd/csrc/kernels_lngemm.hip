@@ -853,8 +853,8 @@ int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st) {
   // PRE: linear2 of the previous layer as the GEMM prologue of in_proj (from layer 1 on) and of the head, always but behind the fused FFN.
   //   split   in_proj <1, 2, 0|1, 3, 3> (<1, 0, 0|1, 3, 3> under LDM_X3_ATTNOUT=0), linear1 <0, 1, 0, 3, 3>, head <0, 0, 1, 3, 3>          6
   //   mixed   in_proj <1, 2, 0|1, 2, 2>, linear1 <0, 1, 0, 2, 2>, head <0, 0, 1, 2, 2>                                                   4
-  //   hybrid  FFN behind the attention (default): in_proj = mixed's layer-0 form, head <0, 0, 0, 1, 1>; two-launch FFN (LDM_HYB_FFN=0,
-  //           d_ff % 32 != 0): in_proj <1, 2, 1, 2, 1> from layer 1 on, linear1 <0, 3, 0, 1, 1>, head <0, 0, 1, 1, 1>                   4
+  //   hybrid  FFN behind the attention (default): in_proj = mixed's layer-0 form, head <0, 0, 0, 1, 1>; two-launch FFN (LDM_HYB_FFN=0):
+  //           in_proj <1, 2, 1, 2, 1> from layer 1 on, linear1 <0, 3, 0, 1, 1>, head <0, 0, 1, 1, 1>                   4
   void (*kern)(LnGemmArgs) = nullptr;
   const bool ffn1 = half_out && !panel && !hi_only && !pre;   // linear1 + ReLU, hi / lo rows or panels (OUT = 1)
   const bool head = !half_out && !a.ada;

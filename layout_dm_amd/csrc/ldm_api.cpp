@@ -205,7 +205,9 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     // in_proj, or the head) instead of as a gemm16x3_k launch: 28 us per layer cheaper than the two launches it replaces, +4 % whole-job
     // same-box.  Fusing out_proj the same way saved nothing per launch and cost the overlap between the two chunk pipelines (a fused launch
     // fills every CU alone): -5 % (profiles/r05_call24_31_*); the attention + out_proj launch below replaced it.
-    h->hid_panels = h->lngemm && h->panel_rows <= (size_t)round_up((int)Mc, 256) + 64 && knob_int("LDM_X3_HIDPANEL", 1) != 0;
+    // (a panel is one whole 32-column tile of linear1: d_ff % 32 != 0 keeps the row-major form — launch_lngemm16x3 refuses panels with a
+    //  partly masked last tile, and the hybrid mode, which needs the panels, is then refused below)
+    h->hid_panels = h->lngemm && h->F % 32 == 0 && h->panel_rows <= (size_t)round_up((int)Mc, 256) + 64 && knob_int("LDM_X3_HIDPANEL", 1) != 0;
     // r06: attention + out_proj as one layout-resident launch behind an in_proj that writes hi / lo panels (kernels_attnout.hip);
     // LDM_DEV=1 LDM_X3_ATTNOUT=0: attn16x3_k + the out_proj launch of gemm16x3_k (the r05 structure)
     h->attnout = h->lngemm && h->ws[0].qkvp_hi && h->panel_rows * 64 * 2 < (1ull << 32) && knob_int("LDM_X3_ATTNOUT", 1) != 0;
@@ -216,7 +218,10 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
       h->np_ffn = mixed == 2 ? 1 : 2;
       h->ffn_fused = mixed == 2 && h->F % 32 == 0 && h->F <= 2048 && knob_int("LDM_HYB_FFN", 1) != 0;
     }
-    if (mixed && !h->w2p) {
+    if (mixed == 2 && !h->w2p && h->lngemm && h->attnout && h->F % 32) {
+      h->err = "precision hybrid: d_ff must be a multiple of 32 (its plain-fp16 hidden activations travel as 32-column panels); use precision mixed or split";
+      rc = -1;
+    } else if (mixed && !h->w2p) {
       h->err = "precision mixed / hybrid: only the reference backbone's geometry (d_model 464, 8 heads, <= 128 tokens per layout) has the two-product kernels; use precision split";
       rc = -1;
     }

@@ -172,14 +172,73 @@ static int denoise_chunk_tiled(ldm_handle* h, Workspace& ws, const int32_t* d_to
 }
 
 // ------------------------------------------------------------------------------------------ row-resident (split / mixed / hybrid on the reference's backbone)
+// The LnGemmArgs of the row-resident launches, one builder per launch: denoise_chunk_row_resident below runs them on a lane's workspace, the
+// development hook ldm_dev_lngemm_run (ldm_dev.cpp, tests/test_lngemm_gpu.py) on the caller's buffers — the same arguments but for the
+// pointers `ws` holds and M.
 // linear2 of layer `w` (+ bias + the residual Q) as the GEMM prologue of the launch that normalises its sum
-static void ffn2_prologue(ldm_handle* h, Workspace& ws, const LayerW& w, LnGemmArgs& a) {
+static void ffn2_prologue(const ldm_handle* h, const Workspace& ws, const LayerW& w, LnGemmArgs& a) {
   a.preA = ws.hid16; a.preAlo = ws.hid16lo; a.pre_lda = h->Fp; a.pre_astages = h->Fp / 32; a.pre_stages = ldm_pack::x3_slab_stages(h->Fp);
   a.pre_img = (const char*)w.x3_ffn2_slab; a.pre_bias = w.b2; a.pre_scale = w.s2;
   a.pre_res = ws.Q;
   a.pre_panel_stride = h->hid_panels ? h->panel_rows * 64 : 0;
   a.np_pre = h->np_ffn;
   if (h->np_ffn == 1) a.preAlo = nullptr;   // (plain-fp16 hidden activations: linear1 wrote no lo panels)
+}
+
+// AdaLN of layer i at timestep t (layer 0: fused with the embedding gather) + QKV projection; P <- normed x (the residual base).
+// pre: x = Q + hid · W2^T + b2 of the PREVIOUS layer, computed in this launch (never stored)
+LnGemmArgs ldm_host::lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre) {
+  const int D = h->D;
+  const LayerW& w = h->layers[i];
+  const float* ss = h->adaln + ((size_t)t * h->L + i) * 2 * D;
+  LnGemmArgs a{};
+  a.x = ws.P; a.ldx = D;
+  a.tokens = (i == 0) ? d_tokens : nullptr;
+  a.emb = h->emb; a.pos = h->pos; a.S = h->S;
+  a.p0 = ss; a.p1 = ss + D; a.ada = 1;
+  a.y32 = ws.P;
+  a.out_scale = w.s_in;
+  a.M = M; a.D = D; a.np_main = h->np_w;
+  if (h->attnout) {   // q / k / v as head-padded hi / lo panels for the fused attention + out_proj launch
+    a.img = (const char*)w.x3_qkv_pad; a.n_tiles = 3 * h->H * 2;
+    a.bias = w.b_in_pad; a.N = 3 * h->H * 64;
+    a.C16 = ws.qkvp_hi; a.C16lo = ws.qkvp_lo; a.panel_out = 1; a.panel_stride = h->panel_rows * 64;
+  } else {
+    a.img = (const char*)w.x3_qkv; a.n_tiles = h->x3_qkv_tiles;
+    a.bias = w.b_in; a.N = 3 * D;
+    a.C32 = ws.qkv32; a.ldc32 = 3 * D;
+  }
+  if (pre) ffn2_prologue(h, ws, h->layers[i - 1], a);
+  return a;
+}
+
+// LayerNorm 2 + FFN1 + ReLU of layer i: hi / lo hidden activations out
+LnGemmArgs ldm_host::lngemm_linear1_args(const ldm_handle* h, const Workspace& ws, int i, int M) {
+  const LayerW& w = h->layers[i];
+  LnGemmArgs a{};
+  a.x = ws.Q; a.ldx = h->D;
+  a.p0 = w.g2; a.p1 = w.be2; a.ada = 0;
+  a.img = (const char*)w.x3_ffn1; a.n_tiles = h->x3_ffn1_tiles;
+  a.bias = w.b1; a.out_scale = w.s1; a.relu = 1;
+  a.C16 = ws.hid16; a.C16lo = ws.hid16lo; a.ldc16 = h->Fp;
+  if (h->hid_panels) { a.panel_out = 1; a.panel_stride = h->panel_rows * 64; }   // (read back by ffn2_prologue in the same form)
+  a.M = M; a.N = h->F; a.D = h->D; a.S = h->S; a.np_main = h->np_ffn;
+  if (h->np_ffn == 1) a.C16lo = nullptr;   // hybrid: ReLU output rounded once (panel-major: ldm_create requires hid_panels for it)
+  return a;
+}
+
+// head: LayerNorm + vocabulary projection (no bias); pre: behind the last layer's linear2
+LnGemmArgs ldm_host::lngemm_head_args(const ldm_handle* h, const Workspace& ws, int M, bool pre) {
+  LnGemmArgs a{};
+  a.x = ws.P; a.ldx = h->D;
+  a.p0 = h->head_g; a.p1 = h->head_b; a.ada = 0;
+  a.img = (const char*)h->x3_head; a.n_tiles = h->x3_head_tiles;
+  a.out_scale = h->head_s;
+  a.C32 = ws.logits; a.ldc32 = h->Cp;
+  a.np_main = h->np_ffn;
+  a.M = M; a.N = h->Cp; a.D = h->D; a.S = h->S;   // (columns C .. Cp of the image are zero rows: exact zeros in the padding)
+  if (pre) ffn2_prologue(h, ws, h->layers[h->L - 1], a);
+  return a;
 }
 
 // The LayerNorm-fed GEMMs as ONE row-resident launch each (kernels_lngemm.hip), attention + out_proj as one layout-resident launch
@@ -190,27 +249,9 @@ static int denoise_chunk_row_resident(ldm_handle* h, Workspace& ws, const int32_
   const bool pre_ffn2 = !h->ffn_fused;
   for (int i = 0; i < h->L; ++i) {
     const LayerW& w = h->layers[i];
-    const float* ss = h->adaln + ((size_t)t * h->L + i) * 2 * D;
-    {  // AdaLN (layer 0: fused with the embedding gather) + QKV projection; P <- normed x (the residual base)
-      LnGemmArgs a{};
-      a.x = ws.P; a.ldx = D;
-      a.tokens = (i == 0) ? d_tokens : nullptr;
-      a.emb = h->emb; a.pos = h->pos; a.S = h->S;
-      a.p0 = ss; a.p1 = ss + D; a.ada = 1;
-      a.y32 = ws.P;
-      a.out_scale = w.s_in;
-      a.M = M; a.D = D; a.np_main = h->np_w;
-      if (h->attnout) {   // q / k / v as head-padded hi / lo panels for the fused attention + out_proj launch
-        a.img = (const char*)w.x3_qkv_pad; a.n_tiles = 3 * h->H * 2;
-        a.bias = w.b_in_pad; a.N = 3 * h->H * 64;
-        a.C16 = ws.qkvp_hi; a.C16lo = ws.qkvp_lo; a.panel_out = 1; a.panel_stride = h->panel_rows * 64;
-      } else {
-        a.img = (const char*)w.x3_qkv; a.n_tiles = h->x3_qkv_tiles;
-        a.bias = w.b_in; a.N = 3 * D;
-        a.C32 = ws.qkv32; a.ldc32 = 3 * D;
-      }
-      const bool pre = pre_ffn2 && i > 0;   // x = Q + hid · W2^T + b2 of the PREVIOUS layer, computed in this launch (never stored)
-      if (pre) ffn2_prologue(h, ws, h->layers[i - 1], a);
+    {
+      const bool pre = pre_ffn2 && i > 0;
+      const LnGemmArgs a = lngemm_in_proj_args(h, ws, d_tokens, t, i, M, pre);
       ldm_handle::Scope sc(h, st, pre ? "gemm_ffn2_qkv_ln" : "gemm_qkv_ln", gemm_flops(M, 3 * D, D) + (pre ? gemm_flops(M, D, F) : 0.0),
                            (double)M * D * 8 + (double)M * 3 * D * 4 + (pre ? (double)M * F * 4 : 0.0));
       if (launch_lngemm16x3(a, st)) return h->fail(-4, "row-resident LayerNorm + GEMM: geometry not supported");
@@ -233,30 +274,13 @@ static int denoise_chunk_row_resident(ldm_handle* h, Workspace& ws, const int32_
       return rc;
     }
     if (h->ffn_fused) continue;   // (the FFN ran behind the attention)
-    {  // LayerNorm 2 + FFN1 + ReLU: hi / lo hidden activations out
-      LnGemmArgs a{};
-      a.x = ws.Q; a.ldx = D;
-      a.p0 = w.g2; a.p1 = w.be2; a.ada = 0;
-      a.img = (const char*)w.x3_ffn1; a.n_tiles = h->x3_ffn1_tiles;
-      a.bias = w.b1; a.out_scale = w.s1; a.relu = 1;
-      a.C16 = ws.hid16; a.C16lo = ws.hid16lo; a.ldc16 = h->Fp;
-      if (h->hid_panels) { a.panel_out = 1; a.panel_stride = h->panel_rows * 64; }   // (read back by ffn2_prologue in the same form)
-      a.M = M; a.N = F; a.D = D; a.S = h->S; a.np_main = h->np_ffn;
-      if (h->np_ffn == 1) a.C16lo = nullptr;   // hybrid: ReLU output rounded once (panel-major: ldm_create requires hid_panels for it)
+    {
+      const LnGemmArgs a = lngemm_linear1_args(h, ws, i, M);
       ldm_handle::Scope sc(h, st, "gemm_ffn1_ln", gemm_flops(M, F, D), (double)M * D * 4 + (double)M * F * 4);
       if (launch_lngemm16x3(a, st)) return h->fail(-4, "row-resident LayerNorm + GEMM: geometry not supported");
     }
   }
-  // head: LayerNorm + vocabulary projection (no bias), behind the last layer's linear2
-  LnGemmArgs a{};
-  a.x = ws.P; a.ldx = D;
-  a.p0 = h->head_g; a.p1 = h->head_b; a.ada = 0;
-  a.img = (const char*)h->x3_head; a.n_tiles = h->x3_head_tiles;
-  a.out_scale = h->head_s;
-  a.C32 = ws.logits; a.ldc32 = h->Cp;
-  a.np_main = h->np_ffn;
-  a.M = M; a.N = h->Cp; a.D = D; a.S = h->S;   // (columns C .. Cp of the image are zero rows: exact zeros in the padding)
-  if (pre_ffn2) ffn2_prologue(h, ws, h->layers[h->L - 1], a);
+  const LnGemmArgs a = lngemm_head_args(h, ws, M, pre_ffn2);
   ldm_handle::Scope sc(h, st, pre_ffn2 ? "gemm_ffn2_head_ln" : "gemm_head_ln", gemm_flops(M, C, D) + (pre_ffn2 ? gemm_flops(M, D, F) : 0.0),
                        (double)M * D * 4 + (double)M * C * 4 + (pre_ffn2 ? (double)M * F * 4 : 0.0));
   if (launch_lngemm16x3(a, st)) return h->fail(-4, "row-resident LayerNorm + GEMM: geometry not supported");

@@ -1,12 +1,14 @@
 // Development hooks of libldm_hip.so (NOT part of the public ABI in include/ldm_hip.h): the s_memtime phase sums of the instrumented
 // kernels (tools/phase_probe.py, lngemm_probe.py, attnout_probe.py) and a unit check of the fused attention + out_proj launch on
-// synthetic operands (tests/test_attnout_gpu.py).  Nothing in the product path calls into this file.
+// synthetic operands (tests/test_attnout_gpu.py), and one row-resident LayerNorm + GEMM launch of a live handle on the caller's rows
+// (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py).  Nothing in the product path calls into this file.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "ldm_handle.h"
 #include "ldm_kernels.h"
 
 using namespace ldm;
@@ -163,5 +165,62 @@ extern "C" int ldm_dev_attnout_check(int B, int S, float qk_amp, uint32_t seed, 
   err_out[0] = e_full / mag;
   err_out[1] = e_hi / mag;
   err_out[2] = mag;
+  return 0;
+}
+
+// ONE lngemm16x3_k launch (kernels_lngemm.hip) of a live handle on the caller's device buffers: the arguments are the product's own
+// (ldm_denoise.cpp lngemm_*_args: the handle's images, pre-scales, parameter tables and mode) with the workspace pointers and M swapped for
+// the caller's.  No reference arithmetic here: tests/_lngemm_cases.py holds the float64 side.  0 on success; -1 when the handle has no
+// row-resident kernels, the requested form does not exist for it, or launch_lngemm16x3 refuses the arguments; -2 on a HIP error.
+struct ldm_dev_lngemm_io {
+  int32_t launch;            // 0 AdaLN + in_proj of `layer` at timestep `t` | 1 norm2 + linear1 + ReLU of `layer` | 2 head LayerNorm + head
+  int32_t layer, t;
+  int32_t prologue;          // linear2 of the preceding layer (in_proj: layer - 1; the head: the last layer) in front of the LayerNorm
+  int32_t M;
+  int32_t pre_lda;           // row-major hidden activations: halves per row (0: the handle's Fp)
+  const int32_t* tokens;     // [M]: in_proj of layer 0 gathers its rows
+  const float* x;            // [M, 464] rows (no tokens, no prologue)
+  const __half *hid_hi, *hid_lo;   // prologue: hidden activations in the form the handle keeps (panels or rows; lo unused in the one-product form)
+  const float* res;          // prologue: fp32 residual rows [M, 464]
+  float* y32;                // in_proj: AdaLN(x) [M, 464] (may alias x)
+  float* C32;                // fp32 output rows [M, ldc32]
+  __half *C16, *C16lo;       // fp16 hi / lo output, rows [M, ldc16] or panels
+  int64_t ldc32, ldc16;      // 0: the product's
+  uint64_t panel_stride;     // bytes between output panels (0: the product's)
+  uint64_t pre_panel_stride; // bytes between hidden panels of the prologue (0: the product's)
+};
+extern "C" int ldm_dev_lngemm_run(ldm_handle* h, const ldm_dev_lngemm_io* io) {
+  if (!h || !io) return -1;
+  if (!h->finalized) return h->fail(-1, "weights not finalized");
+  if (!h->lngemm) return h->fail(-1, "the handle has no row-resident LayerNorm + GEMM kernels");
+  if (io->M < 1 || io->launch < 0 || io->launch > 2) return h->fail(-1, "ldm_dev_lngemm_run: bad launch / M");
+  const bool in_proj = io->launch == 0, lin1 = io->launch == 1, pre = io->prologue != 0;
+  if (in_proj && (io->layer < 0 || io->layer >= h->L || io->t < 0 || io->t >= h->T)) return h->fail(-1, "ldm_dev_lngemm_run: layer / timestep out of range");
+  if (lin1 && (io->layer < 0 || io->layer >= h->L)) return h->fail(-1, "ldm_dev_lngemm_run: layer out of range");
+  // the forms the handle's own pass runs: no linear1 / linear2 launches behind the fused FFN, linear2 in front of in_proj from layer 1 on
+  if ((lin1 || pre) && h->ffn_fused) return h->fail(-1, "ldm_dev_lngemm_run: the handle's FFN runs behind the attention");
+  if (pre && (lin1 || (in_proj && io->layer < 1))) return h->fail(-1, "ldm_dev_lngemm_run: no prologue in front of this launch");
+  ON_DEVICE(h);
+  Workspace ws{};   // the launch's view of the caller's buffers, under the names the product's pass gives them
+  ws.P = in_proj ? io->y32 : const_cast<float*>(io->x);
+  ws.Q = lin1 ? const_cast<float*>(io->x) : const_cast<float*>(io->res);
+  ws.hid16 = lin1 ? io->C16 : const_cast<__half*>(io->hid_hi);
+  ws.hid16lo = lin1 ? io->C16lo : const_cast<__half*>(io->hid_lo);
+  ws.qkvp_hi = io->C16; ws.qkvp_lo = io->C16lo; ws.qkv32 = io->C32; ws.logits = io->C32;
+  LnGemmArgs a = in_proj ? ldm_host::lngemm_in_proj_args(h, ws, io->tokens, io->t, io->layer, io->M, pre)
+                 : lin1  ? ldm_host::lngemm_linear1_args(h, ws, io->layer, io->M)
+                         : ldm_host::lngemm_head_args(h, ws, io->M, pre);
+  if (in_proj) a.x = io->x;   // (the product normalises P in place; here the rows may come from a buffer of their own)
+  if (io->ldc32) a.ldc32 = (int)io->ldc32;
+  if (io->ldc16) a.ldc16 = (int)io->ldc16;
+  if (io->panel_stride && a.panel_out) a.panel_stride = (size_t)io->panel_stride;
+  if (pre && io->pre_panel_stride && a.pre_panel_stride) a.pre_panel_stride = (size_t)io->pre_panel_stride;
+  if (pre && io->pre_lda) a.pre_lda = io->pre_lda;
+  // the pointers launch_lngemm16x3 does not check itself: the rows (unless gathered or computed by the prologue), y32, an output
+  const bool rows_missing = !a.tokens && !pre && !a.x;
+  if (rows_missing || (a.ada && !a.y32) || (!a.C32 && !a.C16)) return h->fail(-1, "ldm_dev_lngemm_run: null operand");
+  if (launch_lngemm16x3(a, 0)) return h->fail(-1, "row-resident LayerNorm + GEMM: geometry not supported");
+  HIP_OK(h, hipStreamSynchronize(0));
+  HIP_OK(h, hipGetLastError());
   return 0;
 }

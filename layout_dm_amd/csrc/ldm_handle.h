@@ -319,6 +319,10 @@ namespace ldm_host {
 std::string& create_error();   // last ldm_create error of this thread (ldm_last_error(NULL))
 double gemm_flops(int M, int N, int K);
 int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false);
+// the arguments of the row-resident LayerNorm + GEMM launches on workspace `ws` (ldm_denoise.cpp; also ldm_dev.cpp ldm_dev_lngemm_run)
+ldm::LnGemmArgs lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre);
+ldm::LnGemmArgs lngemm_linear1_args(const ldm_handle* h, const Workspace& ws, int i, int M);
+ldm::LnGemmArgs lngemm_head_args(const ldm_handle* h, const Workspace& ws, int M, bool pre);
 void fill_post(ldm_handle* h, ldm::PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off, int Bc);
 int check_ready(ldm_handle* h, int B);
 int check_sampler(ldm_handle* h, const ldm_sampler* s);
