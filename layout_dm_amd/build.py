@@ -95,5 +95,23 @@ def build(force: bool = False, verbose: bool = True) -> str:
     return LIB
 
 
+def device_asm(src: str, asm_path=None, resource_report: bool = False):
+    """The gfx950 assembly of one file of csrc/ under the library's own FLAGS -> (assembly text, compiler output).
+    The one recipe of the static kernel checks (tests/_hostbuild.py kernel_asm) and of the tools that read assembly.
+    asm_path keeps the assembly there; resource_report adds hipcc's per-kernel register / scratch / LDS remarks to the output."""
+    import tempfile
+
+    with tempfile.TemporaryDirectory(prefix="ldm_asm_") as tmp:
+        out = asm_path or os.path.join(tmp, os.path.basename(src) + ".s")
+        cmd = [hipcc(), "-x", "hip", *FLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
+        if resource_report:
+            cmd.append("-Rpass-analysis=kernel-resource-usage")
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if p.returncode != 0 or "error:" in p.stdout:
+            raise RuntimeError(f"hipcc failed on {src}:\n{p.stdout}")
+        with open(out) as fh:
+            return fh.read(), p.stdout
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv))

@@ -1,12 +1,12 @@
 """Shared by test_clustering.py (CPU) and test_clustering_gpu.py: the fixture of tools/make_clustering_golden.py and the host
 build of csrc/ldm_cluster_core.h (tests/cpu_cluster_check.cpp) with one runner per mode of that program."""
 import os
-import subprocess
 
 import numpy as np
 
+import _hostbuild as HB
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpu_cluster_check.cpp")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "clustering", "reference.npz")
 PCT_N, PCT_K = (1, 5, 40, 257, 5000), (2, 32, 256)
 LLOYD_M, LLOYD_NK = (1, 5, 300), ((257, 4), (1000, 32), (5000, 128), (20000, 256))
@@ -25,21 +25,13 @@ def golden():
     return _golden
 
 
-def build_host(tmp, name="cpu_cluster_check", flags=("-O2",)):
-    """-ffp-contract=off: every product and sum rounded, as the device build (the header's pragma covers clang only)"""
-    exe = os.path.join(str(tmp), name)
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, SRC, "-o", exe], check=True, cwd=ROOT)
-    return exe
+def build_host(sanitize=False):
+    """(the builder's -ffp-contract=off: every product and sum rounded, as the device build; the header's pragma covers clang only)"""
+    return HB.host_program("cpu_cluster_check", sanitize=sanitize)
 
 
 def _run(exe, tmp, mode, payload: bytes):
-    inp, outp = os.path.join(str(tmp), f"{mode}.in"), os.path.join(str(tmp), f"{mode}.out")
-    with open(inp, "wb") as f:
-        f.write(payload)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
-    rc = subprocess.run([exe, mode, inp, outp], env=env).returncode
-    with open(outp, "rb") as f:
-        return rc, f.read()
+    return HB.run_host_io(exe, tmp, payload, mode)
 
 
 def i32(*v):

@@ -17,10 +17,12 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_cluster_core.h"
+#include "cpu_check_io.h"
 
 namespace {
 
 namespace K = ldm_cluster;
+using check_io::write_vec;
 
 struct Reader {
   FILE* f;
@@ -33,14 +35,11 @@ struct Reader {
   }
   template <class T>
   std::vector<T> many(size_t n) {
-    std::vector<T> v(n);
-    ok = ok && (n == 0 || fread(v.data(), sizeof(T), n, f) == n);
+    std::vector<T> v;
+    ok = ok && check_io::read_vec(f, v, n);
     return v;
   }
 };
-
-template <class T>
-void put(FILE* f, const T* p, size_t n) { fwrite(p, sizeof(T), n, f); }
 
 // the device's sort: ascending order keys (-0.0 in front of +0.0)
 bool sort_values(std::vector<float>& x, bool clip) {
@@ -86,9 +85,9 @@ int main(int argc, char** argv) {
     if (!lloyd) {
       std::vector<float> centres(k);
       K::percentile_host(u.data(), m, k, centres.data());
-      put(fo, &m, 1), put(fo, centres.data(), k);
+      write_vec(fo, &m, 1), write_vec(fo, centres.data(), k);
     } else if (m < k) {
-      put(fo, &m, 1);
+      write_vec(fo, &m, 1);
       rc = 5;
     } else {
       std::sort(c.begin(), c.end());
@@ -97,7 +96,7 @@ int main(int argc, char** argv) {
       const int32_t n_iter = K::lloyd_host(x.data(), ps.data(), n, k, c.data(), max_iter, tol * K::variance(ps.data(), ps2.data(), n),
                                            trace.data());
       const double inertia = K::inertia_host(x.data(), n, c.data(), k);
-      put(fo, &n_iter, 1), put(fo, &inertia, 1), put(fo, c.data(), k), put(fo, trace.data(), (size_t)n_iter * k);
+      write_vec(fo, &n_iter, 1), write_vec(fo, &inertia, 1), write_vec(fo, c.data(), k), write_vec(fo, trace.data(), (size_t)n_iter * k);
     }
   } else if (!strcmp(mode, "prefix")) {
     const int n = in.one<int32_t>();
@@ -106,7 +105,7 @@ int main(int argc, char** argv) {
     if (!in.ok) return 2;
     std::vector<double> ps(n + 1), ps2(n + 1);
     K::prefix_host(x.data(), n, ps.data(), ps2.data());
-    put(fo, ps.data(), n + 1), put(fo, ps2.data(), n + 1);
+    write_vec(fo, ps.data(), n + 1), write_vec(fo, ps2.data(), n + 1);
   } else if (!strcmp(mode, "pick")) {
     const int n = in.one<int32_t>(), nu = in.one<int32_t>();
     if (!in.ok || n < 1 || nu < 0) return 2;
@@ -114,7 +113,7 @@ int main(int argc, char** argv) {
     if (!in.ok) return 2;
     for (int i = 0; i < nu; ++i) {
       const int64_t idx = K::inverse_cdf_pick(w.data(), n, u[i]);
-      put(fo, &idx, 1);
+      write_vec(fo, &idx, 1);
     }
   } else if (!strcmp(mode, "philox")) {
     const uint64_t state = in.one<uint64_t>();
@@ -124,7 +123,7 @@ int main(int argc, char** argv) {
     if (!in.ok) return 2;
     for (int i = 0; i < m; ++i) {
       const double u = K::uniform(state, (uint32_t)q[4 * i], (uint32_t)q[4 * i + 1], (uint32_t)q[4 * i + 2], (uint32_t)q[4 * i + 3]);
-      put(fo, &u, 1);
+      write_vec(fo, &u, 1);
     }
   } else {
     return 1;

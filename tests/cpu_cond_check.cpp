@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_cond_core.h"
+#include "cpu_check_io.h"
 
 using namespace ldm_condb;
 
@@ -34,7 +35,7 @@ struct Reader {
 
 template <typename T>
 static void put(FILE* f, const T* p, size_t n) {
-  if (n && fwrite(p, sizeof(T), n, f) != n) exit(2);
+  if (!check_io::write_vec(f, p, n)) exit(2);
 }
 
 struct Inputs {
@@ -163,13 +164,12 @@ static void graph(const Inputs& in, const TB* bbox, FILE* out) {
 
 int main(int argc, char** argv) {
   if (argc != 3) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 2);
   Reader r;
   fseek(f, 0, SEEK_END);
   r.buf.resize((size_t)ftell(f));
   fseek(f, 0, SEEK_SET);
-  if (!r.buf.empty() && fread(r.buf.data(), 1, r.buf.size(), f) != r.buf.size()) return 2;
+  if (!check_io::read_vec(f, r.buf, r.buf.size())) return 2;
   fclose(f);
   const int32_t* h = r.take<int32_t>(12);
   const int mode = h[0], f64 = h[1];
@@ -187,8 +187,7 @@ int main(int argc, char** argv) {
   in.keep = h[8] ? r.take<uint8_t>(slots) : nullptr;
   in.noise = h[9] ? r.take<float>(slots * 4) : nullptr;
   in.selection = h[10] ? r.take<uint8_t>((size_t)in.B * 2 * (in.E + 1) * (in.E + 1)) : nullptr;
-  FILE* out = fopen(argv[2], "wb");
-  if (!out) return 2;
+  FILE* out = check_io::open_or_exit(argv[2], "wb", 2);
   if (mode == 0) f64 ? encode(in, (const double*)bbox, out) : encode(in, (const float*)bbox, out);
   else f64 ? graph(in, (const double*)bbox, out) : graph(in, (const float*)bbox, out);
   fclose(out);

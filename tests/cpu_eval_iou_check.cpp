@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_eval_iou_core.h"
+#include "cpu_check_io.h"
 
 namespace {
 
@@ -42,17 +43,10 @@ const double* Set::box<double>(int b, int S) const { return b64.data() + (size_t
 
 bool read_set(FILE* f, Set& s, int f64, int B, int S) {
   s.f64 = f64 != 0;
+  using check_io::read_vec;
   const size_t nb = (size_t)B * S * 4;
-  if (s.f64) {
-    s.b64.resize(nb);
-    if (fread(s.b64.data(), 8, nb, f) != nb) return false;
-  } else {
-    s.b32.resize(nb);
-    if (fread(s.b32.data(), 4, nb, f) != nb) return false;
-  }
-  s.label.resize((size_t)B * S);
-  s.n.resize(B);
-  return fread(s.label.data(), 8, s.label.size(), f) == s.label.size() && fread(s.n.data(), 4, B, f) == (size_t)B;
+  if (!(s.f64 ? read_vec(f, s.b64, nb) : read_vec(f, s.b32, nb))) return false;
+  return read_vec(f, s.label, (size_t)B * S) && read_vec(f, s.n, B);
 }
 
 template <typename C, typename T1, typename T2>
@@ -90,8 +84,7 @@ int run(int mode, const Set& s1, const Set& s2, int B, int S, std::vector<double
 
 int main(int argc, char** argv) {
   if (argc != 3) return 1;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 1;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 1);
   int32_t hdr[5];
   if (fread(hdr, 4, 5, f) != 5) return 2;
   const int mode = hdr[0], B = hdr[3], S = hdr[4];
@@ -112,9 +105,8 @@ int main(int argc, char** argv) {
   } else {
     err = run<double, float, double>(mode, s1, s2, B, S, out);
   }
-  f = fopen(argv[2], "wb");
-  if (!f) return 1;
-  fwrite(out.data(), 8, out.size(), f);
+  f = check_io::open_or_exit(argv[2], "wb", 1);
+  check_io::write_vec(f, out);
   fclose(f);
   return err ? 3 : 0;
 }

@@ -8,11 +8,12 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_post_token.h"
+#include "cpu_check_io.h"
 
 template <typename T>
 static std::vector<T> rd(FILE* f, size_t n) {
-  std::vector<T> v(n);
-  if (n && fread(v.data(), sizeof(T), n, f) != n) {
+  std::vector<T> v;
+  if (!check_io::read_vec(f, v, n)) {
     fprintf(stderr, "short read\n");
     exit(2);
   }
@@ -21,8 +22,7 @@ static std::vector<T> rd(FILE* f, size_t n) {
 
 int main(int argc, char** argv) {
   if (argc != 3) return 1;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 1;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 1);
   const auto hdr = rd<int32_t>(f, 10);
   if (hdr[0] != 0x4C444D31) return 3;
   const int N = hdr[1], C = hdr[2];
@@ -59,9 +59,8 @@ int main(int argc, char** argv) {
     float* work = hdr[9] ? row.data() : sep.data();
     out[i] = hdr[7] ? ldm_post::step_token<true>(a, sc, work) : ldm_post::step_token<false>(a, sc, work);
   }
-  FILE* o = fopen(argv[2], "wb");
-  if (!o) return 1;
-  fwrite(out.data(), sizeof(int32_t), N, o);
+  FILE* o = check_io::open_or_exit(argv[2], "wb", 1);
+  check_io::write_vec(o, out);
   fclose(o);
   return 0;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_refine_core.h"
+#include "cpu_check_io.h"
 
 namespace {
 
@@ -43,8 +44,7 @@ struct DirectTokens {
 
 int main(int argc, char** argv) {
   if (argc != 3) return 1;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 1;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 1);
   int32_t hdr[6];
   float weight;
   if (fread(hdr, 4, 6, f) != 6 || fread(&weight, 4, 1, f) != 1) return 2;
@@ -90,10 +90,9 @@ int main(int argc, char** argv) {
     if (bits[i] != kSentinel) return 3;
   for (size_t i = 0; i < n_out; ++i)
     if (bits[mis + i] == kSentinel) return 4;
-  f = fopen(argv[2], "wb");
-  if (!f) return 1;
-  fwrite(&err, 4, 1, f);
-  fwrite(out, 4, n_out, f);
+  f = check_io::open_or_exit(argv[2], "wb", 1);
+  check_io::write_vec(f, &err, 1);
+  check_io::write_vec(f, out, n_out);
   fclose(f);
   free(raw), free(table), free(seq);
   return 0;

@@ -10,14 +10,11 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_relation_detect_core.h"
+#include "cpu_check_io.h"
 
 namespace {
 
-template <typename T>
-bool read(FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
+using check_io::read_vec;
 
 template <typename TB>
 int run(const std::vector<TB>& box, int64_t n_rows, const std::vector<uint8_t>& canvas, const std::vector<int32_t>& off,
@@ -48,8 +45,7 @@ int run(const std::vector<TB>& box, int64_t n_rows, const std::vector<uint8_t>& 
 
 int main(int argc, char** argv) {
   if (argc != 3) return 1;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 1;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 1);
   int32_t hdr[5];
   if (fread(hdr, 4, 5, f) != 5) return 2;
   const int f64 = hdr[0], n_rows = hdr[1], n_nodes = hdr[2], n_graph = hdr[3], n_edge = hdr[4];
@@ -59,9 +55,9 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> canvas;
   std::vector<int32_t> off, src, dst, attr;
   std::vector<int64_t> first;
-  if (!(f64 ? read(f, b64, (size_t)n_rows * 4) : read(f, b32, (size_t)n_rows * 4))) return 2;
-  if (!read(f, canvas, n_nodes) || !read(f, off, (size_t)n_graph + 1) || !read(f, src, n_edge) || !read(f, dst, n_edge) ||
-      !read(f, attr, n_edge) || !read(f, first, n_graph))
+  if (!(f64 ? read_vec(f, b64, (size_t)n_rows * 4) : read_vec(f, b32, (size_t)n_rows * 4))) return 2;
+  if (!read_vec(f, canvas, n_nodes) || !read_vec(f, off, (size_t)n_graph + 1) || !read_vec(f, src, n_edge) ||
+      !read_vec(f, dst, n_edge) || !read_vec(f, attr, n_edge) || !read_vec(f, first, n_graph))
     return 2;
   fclose(f);
   for (int g = 0; g < n_graph; ++g)
@@ -70,10 +66,9 @@ int main(int argc, char** argv) {
   std::vector<float> score(n_graph);
   const int err = f64 ? run(b64, n_rows, canvas, off, src, dst, attr, first, edge, score)
                       : run(b32, n_rows, canvas, off, src, dst, attr, first, edge, score);
-  f = fopen(argv[2], "wb");
-  if (!f) return 1;
-  fwrite(edge.data(), 4, edge.size(), f);
-  fwrite(score.data(), 4, score.size(), f);
+  f = check_io::open_or_exit(argv[2], "wb", 1);
+  check_io::write_vec(f, edge);
+  check_io::write_vec(f, score);
   fclose(f);
   return err;
 }

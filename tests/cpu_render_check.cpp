@@ -11,14 +11,11 @@
 #include <vector>
 
 #include "../layout_dm_amd/csrc/ldm_render_core.h"
+#include "cpu_check_io.h"
 
 namespace {
 
-template <typename T>
-bool read(FILE* f, std::vector<T>& v, size_t n) {
-  v.resize(n);
-  return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
-}
+using check_io::read_vec;
 
 template <typename TB>
 int render(const std::vector<TB>& box, const std::vector<int64_t>& label, const std::vector<uint8_t>& mask,
@@ -69,8 +66,7 @@ int render(const std::vector<TB>& box, const std::vector<int64_t>& label, const 
 
 int main(int argc, char** argv) {
   if (argc != 3) return 1;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 1;
+  FILE* f = check_io::open_or_exit(argv[1], "rb", 1);
   int32_t hdr[8];
   if (fread(hdr, 4, 8, f) != 8) return 2;
   const int f64 = hdr[0], B = hdr[1], S = hdr[2], n_colors = hdr[3], H = hdr[4], W = hdr[5], cols = hdr[6], pad = hdr[7];
@@ -82,16 +78,15 @@ int main(int argc, char** argv) {
   std::vector<int64_t> label;
   std::vector<uint8_t> mask, colors;
   const size_t n = (size_t)B * S;
-  if (!(f64 ? read(f, b64, n * 4) : read(f, b32, n * 4))) return 2;
-  if (!read(f, label, n) || !read(f, mask, n) || !read(f, colors, (size_t)n_colors * 3)) return 2;
+  if (!(f64 ? read_vec(f, b64, n * 4) : read_vec(f, b32, n * 4))) return 2;
+  if (!read_vec(f, label, n) || !read_vec(f, mask, n) || !read_vec(f, colors, (size_t)n_colors * 3)) return 2;
   fclose(f);
   std::vector<uint8_t> out((size_t)GH * (size_t)GW * 3, 0);
   const int32_t err = f64 ? render(b64, label, mask, colors, B, S, n_colors, H, W, cols, pad, GW, out)
                           : render(b32, label, mask, colors, B, S, n_colors, H, W, cols, pad, GW, out);
-  f = fopen(argv[2], "wb");
-  if (!f) return 1;
-  fwrite(&err, 4, 1, f);
-  fwrite(out.data(), 1, out.size(), f);
+  f = check_io::open_or_exit(argv[2], "wb", 1);
+  check_io::write_vec(f, &err, 1);
+  check_io::write_vec(f, out);
   fclose(f);
   return 0;
 }

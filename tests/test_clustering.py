@@ -5,19 +5,18 @@ tests/cpu_cluster_check.cpp) against the fixture of tools/make_clustering_golden
 pattern equal, centres within the recorded ulp distance + 1) and scikit-learn's explicit-start Lloyd (centres to 1e-12, n_iter
 equal, direct-pass inertia to 1e-9).  Hand-made rows for the documented rules (a point on a midpoint, a cluster that empties,
 k = 1, n = k, all values equal, NaN), the Philox stream against a numpy restatement, the
-inverse-CDF pick on hand-given uniforms.  The same program under -fsanitize=address,undefined.  The exports, their refusals,
+inverse-CDF pick on hand-given uniforms.  The same program as the ASan + UBSan build.  The exports, their refusals,
 the kernels' resource report, and the Python API: its refusals (a float64 that is no float32 among them) and its raising without a GPU."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import _clustering_cases as CC
+import _hostbuild as HB
 
 ROOT = CC.ROOT
 NEW_EXPORTS = ("ldm_cluster_workspace_bytes", "ldm_cluster_sort", "ldm_kmeans1d_fit", "ldm_kmeans1d_lloyd", "ldm_percentile_fit",
@@ -25,14 +24,13 @@ NEW_EXPORTS = ("ldm_cluster_workspace_bytes", "ldm_cluster_sort", "ldm_kmeans1d_
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    return CC.build_host(tmp_path_factory.mktemp("cluster"))
+def host_exe():
+    return CC.build_host()
 
 
 @pytest.fixture(scope="module")
-def san_exe(tmp_path_factory):
-    return CC.build_host(tmp_path_factory.mktemp("cluster_san"), "cpu_cluster_check_san",
-                         ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
+def san_exe():
+    return CC.build_host(sanitize=True)
 
 
 def test_feature_is_present():
@@ -191,7 +189,7 @@ def test_host_prefix_sums_against_cumsum(host_exe, tmp_path):
 
 
 def test_host_build_under_address_and_undefined_sanitizers(san_exe, tmp_path):
-    """the same cases with the stand-alone program built with -fsanitize=address,undefined: every array is an exact-size
+    """the same cases with the stand-alone program as the ASan + UBSan build: every array is an exact-size
     std::vector or new[], so a read or write past one, signed overflow or a bad shift ends the run with a non-zero code"""
     _percentile_fixture(san_exe, tmp_path)
     _lloyd_fixture(san_exe, tmp_path)
@@ -280,16 +278,8 @@ def test_python_api_refusals_and_no_silent_cpu_path():
                 call()
 
 
-def test_cluster_kernels_use_no_scratch_and_no_float_atomics(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    asm_path = tmp_path / "cluster.s"
-    out = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o",
-                          str(asm_path), os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_cluster.hip"),
-                          "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900).stdout
-    assert "error:" not in out, out
+def test_cluster_kernels_use_no_scratch_and_no_float_atomics():
+    asm, out, _ = HB.kernel_asm("kernels_cluster.hip", resource_report=True)
     blocks = re.split(r"Function Name: ", out)[1:]
     assert len(blocks) >= 18
     for blk in blocks:
@@ -297,7 +287,7 @@ def test_cluster_kernels_use_no_scratch_and_no_float_atomics(tmp_path):
         assert get(r"ScratchSize \[bytes/lane\]: (\d+)") == 0, blk
         assert get(r"VGPRs? Spill: (\d+)") == 0 and get(r"SGPRs? Spill: (\d+)") == 0, blk
         assert get(r"LDS Size \[bytes/block\]: (\d+)") <= 65536, blk
-    ins = [ln.split(";")[0].strip() for ln in asm_path.read_text().splitlines()]
+    ins = [ln.split(";")[0].strip() for ln in asm.splitlines()]
     ops = {i.split()[0] for i in ins if i and not i.startswith((".", "_", "$")) and not i.endswith(":")}
     # determinism: no floating-point atomic of any memory space; the integer LDS add of the radix histogram is the only atomic
     assert not [o for o in ops if re.search(r"(atomic|ds)_(pk_)?(add|min|max)_(rtn_)?f(16|32|64)", o) or "atomic_pk" in o], ops

@@ -28,8 +28,8 @@ def cuda():
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    return CC.build_host(tmp_path_factory.mktemp("cluster_gpu"))
+def host_exe():
+    return CC.build_host()   # (the plain build: no sanitizer next to a GPU)
 
 
 @pytest.fixture(scope="module")

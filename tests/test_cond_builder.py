@@ -9,24 +9,21 @@ exactly 0 / 1, w / h below d; float32 and float64) are held against torch execut
 Also: the documented kmeans / percentile rules, every error bit on a hand-made bad input, and the C-ABI exports."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _hostbuild as HB
+
 N_CATEGORY, N_BIN, E = 25, 32, 25
 PAD, MASK = N_CATEGORY + 4 * N_BIN, N_CATEGORY + 4 * N_BIN + 1
 RULES = {"gt": 0, "c": 1, "cwh": 2, "partial": 3, "refinement": 4, "relation": 5}
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("cond_builder") / "cpu_cond_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpu_cond_check.cpp"),
-                    "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def host_exe():
+    return HB.host_program("cpu_cond_check")
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +39,16 @@ def host_run(exe, tmp_path, mode, bbox, label, mask, *, n_category=N_CATEGORY, n
              keep=None, noise=None, selection=None, edge_ratio=0.1, seed=0, first_layout=0):
     B, S = label.shape
     f64 = bbox.dtype == np.float64
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([mode, f64, B, S, n_category, n_bin, quant, rule, keep is not None, noise is not None,
-                          selection is not None, 0], np.int32).tobytes())
-        f.write(np.array([edge_ratio], np.float64).tobytes() + np.array([seed, first_layout], np.uint64).tobytes())
-        for a, dt in ((bbox, bbox.dtype), (label, np.int64), (mask, np.uint8), (centres, np.float64), (keep, np.uint8),
-                      (noise, np.float32), (selection, np.uint8)):
-            if a is not None:
-                f.write(_pad8(np.ascontiguousarray(a, dt).tobytes()))
-    rc = subprocess.run([exe, str(inp), str(outp)]).returncode
+    payload = np.array([mode, f64, B, S, n_category, n_bin, quant, rule, keep is not None, noise is not None,
+                        selection is not None, 0], np.int32).tobytes()
+    payload += np.array([edge_ratio], np.float64).tobytes() + np.array([seed, first_layout], np.uint64).tobytes()
+    for a, dt in ((bbox, bbox.dtype), (label, np.int64), (mask, np.uint8), (centres, np.float64), (keep, np.uint8),
+                  (noise, np.float32), (selection, np.uint8)):
+        if a is not None:
+            payload += _pad8(np.ascontiguousarray(a, dt).tobytes())
+    rc, raw = HB.run_host_io(exe, tmp_path, payload)
     assert rc == 0
-    raw = np.fromfile(outp, np.uint8)
+    raw = np.frombuffer(raw, np.uint8)
     at = [0]
 
     def take(dt, n):
@@ -311,6 +306,23 @@ def test_host_own_draws_have_the_reference_counts(host_exe, tmp_path):
         assert per[b] == int(2 * (N * (N - 1) // 2) * 0.1), (b, n[b], per[b])
     other = host_run(host_exe, tmp_path, 1, bbox, label, mask, seed=12)
     assert not np.array_equal(other["edge_index"], g["edge_index"])
+
+
+def test_host_build_under_address_and_undefined_sanitizers(tmp_path, getcond):
+    """every host-build case above on the ASan + UBSan build: the program reads its arrays from one exact-size buffer, and the
+    graph builder fills per-layout arrays of n_pairs entries by pair_of's index arithmetic"""
+    exe = HB.host_program("cpu_cond_check", sanitize=True)
+    for ctype in ("c", "cwh", "partial", "relation"):
+        test_host_build_reproduces_the_reference_get_cond(exe, tmp_path, getcond, ctype)
+    test_host_build_reproduces_the_reference_relation_graph(exe, tmp_path, getcond)
+    for T in (np.float32, np.float64):
+        test_linear_bin_boundaries_follow_torch(exe, tmp_path, T)
+    test_refinement_rule_and_noise_sum(exe, tmp_path, getcond)
+    test_kmeans_and_percentile_rules(exe, tmp_path)
+    test_percentile_sentinel_centres_are_part_of_the_search(exe, tmp_path)
+    test_every_error_bit_fires(exe, tmp_path)
+    test_zero_element_layout(exe, tmp_path)
+    test_host_own_draws_have_the_reference_counts(exe, tmp_path)
 
 
 def test_exports_and_bad_arguments():

@@ -7,10 +7,11 @@ float32 x float64 call).  Also: the fixture's inputs are reproducible from the g
 bit for bit where the reference is importable, and the C-ABI exports the three entry points and refuses bad arguments."""
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import _hostbuild as HB
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL = {"f32": 1e-6, "f64": 1e-12, "mix": 1e-12}
@@ -43,11 +44,8 @@ def _close(a, b, rtol, what):
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("eval_iou") / "cpu_eval_iou_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpu_eval_iou_check.cpp"),
-                    "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def host_exe():
+    return HB.host_program("cpu_eval_iou_check")
 
 
 def _pack(layouts, S):
@@ -64,14 +62,10 @@ def _host(exe, tmp_path, mode, set1, set2=None, S=None):
     set2 = set1 if set2 is None else set2
     S = S or max(1, max(len(l) for _, l in set1 + set2))
     p1, p2 = _pack(set1, S), _pack(set2, S)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([mode, p1[0], p2[0], len(set1), S], np.int32).tobytes())
-        for p in (p1, p2):
-            for a in p[1:]:
-                f.write(np.ascontiguousarray(a).tobytes())
-    r = subprocess.run([exe, str(inp), str(outp)])
-    return r.returncode, np.fromfile(outp, np.float64)
+    payload = np.array([mode, p1[0], p2[0], len(set1), S], np.int32).tobytes()
+    payload += b"".join(np.ascontiguousarray(a).tobytes() for p in (p1, p2) for a in p[1:])
+    rc, raw = HB.run_host_io(exe, tmp_path, payload)
+    return rc, np.frombuffer(raw, np.float64)
 
 
 def _sorted(layout):
@@ -212,6 +206,20 @@ def test_nan_iou_sets_the_error_flag(host_exe, tmp_path):
     z = np.zeros((2, 4))   # two zero-area boxes at the same spot: IoU 0 / 0
     rc, _ = _host(host_exe, tmp_path, 2, [(z, np.zeros(2, np.int64))], [(z, np.zeros(2, np.int64))])
     assert rc == 3
+
+
+def test_host_build_under_address_and_undefined_sanitizers(tmp_path, fx):
+    """every host-build case above on the ASan + UBSan build: the solver's state arrays are kMaxS + 1 long, the box, label and
+    count arrays are exact-size allocations"""
+    exe = HB.host_program("cpu_eval_iou_check", sanitize=True)
+    for prec in G.PRECISIONS:
+        test_iou_entries_bit_exact(exe, tmp_path, fx, prec)
+        test_docsim_pairs(exe, tmp_path, fx, prec)
+        test_maxiou_pairs(exe, tmp_path, fx, prec)
+    for prec in ("f32", "f64"):
+        test_average_iou_and_perceptual_entries(exe, tmp_path, fx, prec)
+    test_solver_against_scipy_on_random_matrices(exe, tmp_path)
+    test_nan_iou_sets_the_error_flag(exe, tmp_path)
 
 
 def test_cabi_exports_and_argument_checks():

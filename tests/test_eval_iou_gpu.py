@@ -2,13 +2,13 @@
 layout_dm_amd/metrics.py) against tests/golden/eval_iou/reference.npz, the reference's own results (tools/make_eval_iou_golden.py):
 rtol 1e-5 for float32 inputs, 1e-10 for float64 and the mixed float32 x float64 call.  No reference import here."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _hostbuild as HB
+
 RTOL = {"f32": 1e-5, "f64": 1e-10, "mix": 1e-10}
 PRECISIONS = ("f32", "f64", "mix")
 
@@ -169,19 +169,15 @@ def test_scale_group_of_256_by_256_layouts_s25_vs_host_build(cuda, tmp_path):
     b = [lay(np.float64) for _ in range(300)]
     (_, n1, n2, s), = M.max_iou_pair_scores(a, b)
     assert (n1, n2) == (256, 300) and s.shape == (256 * 300,)
-    exe = tmp_path / "cpu_eval_iou_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "cpu_eval_iou_check.cpp"), "-o", str(exe)],
-                   check=True)
     idx = np.arange(0, len(s), 7)
     srt = lambda x: (x[0][np.argsort(x[1], kind="stable")], np.sort(x[1], kind="stable"))  # noqa: E731
     s1 = [srt(a[k % n1]) for k in idx]
     s2 = [srt(b[k // n1]) for k in idx]
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([2, 0, 1, len(idx), 25], np.int32).tobytes())
-        for ls, dt in ((s1, np.float32), (s2, np.float64)):
-            f.write(np.stack([x for x, _ in ls]).astype(dt).tobytes())
-            f.write(np.stack([l for _, l in ls]).astype(np.int64).tobytes())
-            f.write(np.full(len(ls), 25, np.int32).tobytes())
-    subprocess.run([str(exe), str(inp), str(outp)], check=True)
-    _close(s[idx], np.fromfile(outp, np.float64), 1e-12, "scale")
+    payload = np.array([2, 0, 1, len(idx), 25], np.int32).tobytes()
+    for ls, dt in ((s1, np.float32), (s2, np.float64)):
+        payload += np.stack([x for x, _ in ls]).astype(dt).tobytes()
+        payload += np.stack([l for _, l in ls]).astype(np.int64).tobytes()
+        payload += np.full(len(ls), 25, np.int32).tobytes()
+    rc, raw = HB.run_host_io(HB.host_program("cpu_eval_iou_check"), tmp_path, payload)   # (the plain build: no sanitizer next to a GPU)
+    assert rc == 0, rc
+    _close(s[idx], np.frombuffer(raw, np.float64), 1e-12, "scale")

@@ -8,28 +8,18 @@ insertion cannot see into.  Two failure classes found on hardware this round are
 * VALU write -> MFMA operand read without wait states (an MFMA issued right behind the ``v_cvt_pk`` of its B operand read
   the old register contents: NaNs).  ``s_nop 3`` (4 wait states) is the distance verified on the MI355X.
 """
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+import _hostbuild as HB
 import _x3_sched as x3
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 VALU_TO_MFMA_WAIT_STATES = 4
 
 
-def _compile(src: str, tmp_path) -> str:
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path / (os.path.basename(src) + ".s")
-    subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o",
-                    str(out), os.path.join(ROOT, "layout_dm_amd", "csrc", src), "-Wno-unused-function"],
-                   check=True, capture_output=True, text=True, timeout=900)
-    return out.read_text()
+def _compile(src: str) -> str:
+    return HB.kernel_asm(src)[0]
 
 
 def _kernels(asm: str):
@@ -103,8 +93,8 @@ def _regs(tok: str):
 
 
 @pytest.mark.parametrize("src,kernel_substr", [("kernels_stack.hip", "stack_stream_k")])
-def test_stream_kernels_no_spills_no_valu_mfma_hazard(tmp_path, src, kernel_substr):
-    asm = _compile(src, tmp_path)
+def test_stream_kernels_no_spills_no_valu_mfma_hazard(src, kernel_substr):
+    asm = _compile(src)
     kernels = {k: v for k, v in _kernels(asm).items() if kernel_substr in k}
     assert kernels, "no kernel found"
     # every variant without the probe instrumentation (TM = false: the first template argument mangles as Lb0) must be
@@ -158,12 +148,12 @@ def test_stream_kernels_no_spills_no_valu_mfma_hazard(tmp_path, src, kernel_subs
         assert n_mfma > 150, f"{name}: only {n_mfma} inline-asm MFMAs found (parser broken?)"
 
 
-def test_step_tail_kernels_use_no_scratch(tmp_path):
+def test_step_tail_kernels_use_no_scratch():
     """The other launch of every reverse step (posterior + draw + next step's embedding) and the result packaging: no
     scratch either — a scratch-using kernel between the scratch-free stack kernels slowed the graph-replayed two-lane loop
     (profiles/r02_call35_37_*: the same effect as observed with the wide fp32 GEMM tile)."""
     for src, names in (("kernels_post.hip", ("posterior_sample_k",)), ("kernels_decode.hip", ("decode_layouts_k",))):
-        asm = _compile(src, tmp_path)
+        asm = _compile(src)
         for name in names:
             blocks = re.findall(r"\.amdhsa_kernel\s+(\S*%s\S*)(.*?)\.end_amdhsa_kernel" % name, asm, flags=re.S)
             assert blocks, name
@@ -172,7 +162,7 @@ def test_step_tail_kernels_use_no_scratch(tmp_path):
                 assert m and int(m.group(1)) == 0, (sym, m and m.group(1))
 
 
-def test_exact_mode_gemm_tile_and_attention_resources(tmp_path):
+def test_exact_mode_gemm_tile_and_attention_resources():
     """The exact mode's fp32 kernels: no scratch, and the register / LDS footprints their schedules were measured at —
     the 128 x 128 GEMM tile at <= 102 VGPRs and 32 KB of LDS (5 workgroups per CU) and the
     fp32 attention (K alone in LDS: 30 KB, <= 170 VGPRs: 3 workgroups per CU).  The GEMMs' operands arrive by LDS-DMA."""
@@ -182,7 +172,7 @@ def test_exact_mode_gemm_tile_and_attention_resources(tmp_path):
     }
     asm_of = {}
     for key, w in want.items():
-        asm = asm_of.setdefault(w["src"], _compile(w["src"], tmp_path))
+        asm = asm_of.setdefault(w["src"], _compile(w["src"]))
         blocks = re.findall(r"\.amdhsa_kernel\s+(\S*%s\S*)(.*?)\.end_amdhsa_kernel" % key, asm, flags=re.S)
         assert len(blocks) == 1, (key, [b[0] for b in blocks])
         sym, body = blocks[0]
@@ -196,12 +186,12 @@ def test_exact_mode_gemm_tile_and_attention_resources(tmp_path):
             assert not any(i.startswith("ds_write") for i in ins), sym  # no register staging left
 
 
-def test_split_mode_kernels_resources(tmp_path):
+def test_split_mode_kernels_resources():
     """The split mode's kernels (r04): the production GEMM instantiations (256 x 256 tiles on 8 waves: 128 accumulator
     registers per lane, <= 256 registers = two waves per SIMD, operands by LDS-DMA only, no scratch) and the fp16 x 3
     attention (<= 170 VGPRs: three workgroups per CU; no scratch: a `cond ? *p : zero` load once compiled into a flat load
     of a select between the global pointer and a STACK zero)."""
-    asm = _compile("kernels_gemm16.hip", tmp_path)
+    asm = _compile("kernels_gemm16.hip")
     blocks = re.findall(r"\.amdhsa_kernel\s+(\S*gemm16x3_kILi256ELi256ELi32ELi2ELi2ELi4ELi[0-3]ELi0ELi0E\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S)
     assert len(blocks) == 4, [b[0] for b in blocks]
     get = lambda body, field: int(re.search(r"\.amdhsa_%s\s+(\d+)" % field, body).group(1))
@@ -212,7 +202,7 @@ def test_split_mode_kernels_resources(tmp_path):
         ins = _kernels(asm)[sym]
         assert sum("global_load_lds_dwordx4" in i for i in ins) >= 8, sym
         assert sum("v_mfma_f32_32x32x16_f16" in i or "v_mfma_f32_32x32x16f16" in i for i in ins) >= 48, sym
-    asm = _compile("kernels_attn16.hip", tmp_path)
+    asm = _compile("kernels_attn16.hip")
     blocks = re.findall(r"\.amdhsa_kernel\s+(\S*attn16x3_k\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S)
     assert len(blocks) == 1
     sym, body = blocks[0]
@@ -223,12 +213,12 @@ def test_split_mode_kernels_resources(tmp_path):
     assert sum("v_mfma" in i for i in ins) == 96, sym  # 2 x (4 x 4 | 8 x 2) fragment pairs x 3 products
 
 
-def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards(tmp_path):
+def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards():
     """kernels_lngemm.hip (r05): no scratch; no VALU write of an inline-asm MFMA operand inside the verified wait states; and the
     failure class r05 found on hardware — hipcc reading a tile accumulator right behind the asm MFMAs it cannot recognise (two
     builds lost the low-order products that way: logits error 5e-5 instead of 9e-7) — every non-MFMA instruction that READS the
     destination registers of an inline-asm MFMA must sit at least one whole MFMA (8 passes = 32 cycles) of wait states behind it."""
-    asm = _compile("kernels_lngemm.hip", tmp_path)
+    asm = _compile("kernels_lngemm.hip")
     # the product instantiations (TM = false, ABL = 0: template arguments 3 and 4 mangle as Lb0ELi0; the phase-timer and measurement builds are dev only)
     NAME = re.compile(r"ELb0ELi0ELb([01])ELi([123])ELi([123])EEEvNS_10LnGemmArgsE$")   # ... PRE, NPM, NPP> (products per k16-step: tile loop, GEMM prologue)
     kernels = {k: v for k, v in _kernels(asm).items() if "lngemm16x3_k" in k and NAME.search(k)}
@@ -319,7 +309,7 @@ def test_lngemm_reachable_forms_no_scratch_and_mfma_hazards(tmp_path):
                     break
 
 
-def test_attnout_kernel_register_discipline_and_hazards(tmp_path):
+def test_attnout_kernel_register_discipline_and_hazards():
     """kernels_attnout.hip (r06): every MFMA is inline asm with a pinned accumulator, q fragments arrive by asm global loads hipcc does
     not track.  Checked on the ISA of the product instantiation (TM = false):
       * no scratch; 276 asm MFMAs per head iteration + 48 in the prologue (scores of head 0);
@@ -330,7 +320,7 @@ def test_attnout_kernel_register_discipline_and_hazards(tmp_path):
       * no VALU write of an asm MFMA's operand inside the verified wait states (hipcc had sunk the fp16 casts of the attention output to
         ONE instruction in front of the MFMA that consumes them);
       * a VALU read of an asm MFMA's VGPR result sits at least a whole MFMA behind it."""
-    asm = _compile("kernels_attnout.hip", tmp_path)
+    asm = _compile("kernels_attnout.hip")
     ks = {k: v for k, v in _kernels(asm).items() if "attnout16x3_k" in k}
     names = sorted(k for k in ks if "ILb0E" in k)   # <TM = false, W2 = false | true, FFN = false>: three products in out_proj, or two (Wo fp16 only)
     assert len(names) == 3 and "ILb0ELb0ELb0E" in names[0] and "ILb0ELb1ELb0E" in names[1] and "ILb0ELb1ELb1E" in names[2], list(ks)

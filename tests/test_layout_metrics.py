@@ -7,16 +7,15 @@ identical boxes, zero-area boxes, touching boxes, stale boxes in padded slots).
 GPU: ldm_layout_metrics through the C-ABI against the same fixture and, at the bench's batch size, against the oracle; the
 decode kernel's device output feeds it directly.  fp32 sums in another order than torch's: rtol 1e-5 (observed 2e-7)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _hostbuild as HB
 from oracle import restatement as R
 from oracle.make_golden import metrics_layouts
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("alignment-ACLayoutGAN", "alignment-LayoutGAN++", "alignment-NDN", "overlap-ACLayoutGAN", "overlap-LayoutGAN++",
         "overlap-LayoutGAN")
 RTOL, ATOL = 1e-5, 1e-7
@@ -42,22 +41,16 @@ def test_oracle_restatement_vs_reference_fixture(golden_dir):
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("metrics") / "cpu_metrics_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpu_metrics_check.cpp"), "-o",
-                    str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def host_exe():
+    return HB.host_program("cpu_metrics_check")
 
 
 def _run_host(exe, tmp_path, bbox, mask):
     B, S = mask.shape
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([B, S], np.int32).tobytes())
-        f.write(np.ascontiguousarray(bbox, np.float32).tobytes())
-        f.write(np.ascontiguousarray(mask, np.uint8).tobytes())
-    subprocess.run([exe, str(inp), str(outp)], check=True)
-    return np.fromfile(outp, np.float32).reshape(B, 6)
+    rc, raw = HB.run_host_io(exe, tmp_path, np.array([B, S], np.int32).tobytes() + np.ascontiguousarray(bbox, np.float32).tobytes() +
+                             np.ascontiguousarray(mask, np.uint8).tobytes())
+    assert rc == 0, rc
+    return np.frombuffer(raw, np.float32).reshape(B, 6)
 
 
 def test_kernel_source_on_the_host_vs_reference_fixture_and_oracle(host_exe, tmp_path, golden_dir):
@@ -74,6 +67,12 @@ def test_kernel_source_on_the_host_vs_reference_fixture_and_oracle(host_exe, tmp
         o = R.layout_metrics(bbox, mask)
         for i, k in enumerate(KEYS):
             _close(out[:, i], o[k], (S, k))
+
+
+def test_host_build_under_address_and_undefined_sanitizers(tmp_path, golden_dir):
+    """the same cases on the ASan + UBSan build: element_terms indexes the exact-size box and mask arrays of one layout"""
+    test_kernel_source_on_the_host_vs_reference_fixture_and_oracle(HB.host_program("cpu_metrics_check", sanitize=True), tmp_path,
+                                                                   golden_dir)
 
 
 @pytest.fixture(scope="module")

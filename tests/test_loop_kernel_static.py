@@ -19,14 +19,13 @@ the assembly of the one-pass kernel (HEAD 1) and of the loop kernel (HEAD 2):
 import collections
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import pytest
 
+import _hostbuild as HB
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 KERNELS = {"HEAD1": "_ZN3ldm14stack_stream_kILb0ELi1ELb0EEEvNS_9StackArgsE",
@@ -35,14 +34,8 @@ PARENT_VALU_PER_STEP = 52700
 
 
 @pytest.fixture(scope="module")
-def asm_path(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    out = tmp_path_factory.mktemp("stack_asm") / "kernels_stack.s"
-    subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o", str(out),
-                    os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_stack.hip"), "-Wno-unused-function"],
-                   check=True, capture_output=True, text=True, timeout=900)
-    return str(out)
+def asm_path():
+    return HB.kernel_asm("kernels_stack.hip")[2]   # (the compile test_kernel_asm_lint.py reads, too)
 
 
 def _instructions(asm_path, symbol):

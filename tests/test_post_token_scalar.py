@@ -4,10 +4,9 @@ run against the oracle on states of the REFERENCE's trajectories (tests/golden):
 identical uniforms for random / top-k / top-p, and for gumbel on identical per-class noise words; the same over the
 parameter edges of top-k / top-p / temperature (tests/_sampler_cases.py).  This is the form in which one lane of
 the stack kernel can finish a token behind the fused vocabulary head."""
+import io
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,22 +16,16 @@ from oracle import restatement as R
 from oracle import spec as SP
 from oracle import synth
 
+import _hostbuild as HB
 import _sampler_cases as SC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KINDS = {"deterministic": 0, "random": 1, "top_p": 2, "top_k": 3, "gumbel": 4}
 SCHED_KEYS = ("log_at", "log_bt", "log_ct", "log_cumprod_at", "log_cumprod_bt", "log_cumprod_ct")
 
 
 @pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    exe = tmp_path_factory.mktemp("post_token") / "cpu_post_token_check"
-    subprocess.run([cxx, "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                    os.path.join(ROOT, "tests", "cpu_post_token_check.cpp"), "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def harness():
+    return HB.host_program("cpu_post_token_check", extra=("-Wextra",))
 
 
 def _run(harness, tmp_path, spec, W, tokens, t_post, logits, cfg, step, seed, first_layout, cond=None, f64=False,
@@ -66,8 +59,7 @@ def _run(harness, tmp_path, spec, W, tokens, t_post, logits, cfg, step, seed, fi
         if cond.get("type") == "refinement":
             weak = np.ascontiguousarray(np.asarray(cond["weak_logits"], np.float32).transpose(0, 2, 1)).reshape(N, C)
     layout = (np.repeat(np.arange(B, dtype=np.uint64), S) + np.uint64(first_layout))
-    path_in, path_out = str(tmp_path / "case.bin"), str(tmp_path / "out.bin")
-    with open(path_in, "wb") as f:
+    with io.BytesIO() as f:
         f.write(np.array([0x4C444D31, N, C, spec.pad_id, spec.mask_id, KINDS[cfg["name"]], int(cfg.get("top_k", 1)),
                           1 if f64 else 0, 1 if weak is not None else 0, 1 if alias else 0], np.int32).tobytes())
         f.write(np.array([cfg.get("temperature", 1.0), cfg.get("top_p", 1.0)], np.float32).tobytes())
@@ -80,8 +72,9 @@ def _run(harness, tmp_path, spec, W, tokens, t_post, logits, cfg, step, seed, fi
         f.write(np.ascontiguousarray(logits.numpy().reshape(N, -1)[:, :C], np.float32).tobytes())
         if weak is not None:
             f.write(weak.tobytes())
-    subprocess.run([harness, path_in, path_out], check=True, timeout=120)
-    return torch.from_numpy(np.fromfile(path_out, np.int32).astype(np.int64)).view(B, S)
+        rc, raw = HB.run_host_io(harness, tmp_path, f.getvalue())
+    assert rc == 0, rc
+    return torch.from_numpy(np.frombuffer(raw, np.int32).astype(np.int64)).view(B, S)
 
 
 def _weights(ds):
@@ -127,10 +120,11 @@ def test_scalar_tail_greedy_equals_reference_tokens(harness, tmp_path, golden_di
     assert bad <= (0 if f64 else 2), f"{bad}/{total}"
 
 
-@pytest.mark.parametrize("cfg", [{"name": "random", "temperature": 1.0}, {"name": "random", "temperature": 0.7},
-                                 {"name": "top_k", "top_k": 5, "temperature": 1.0},
-                                 {"name": "top_p", "top_p": 0.9, "temperature": 1.0}],
-                         ids=["random", "random_T0.7", "top_k5", "top_p0.9"])
+DRAW_CFGS = [{"name": "random", "temperature": 1.0}, {"name": "random", "temperature": 0.7},
+             {"name": "top_k", "top_k": 5, "temperature": 1.0}, {"name": "top_p", "top_p": 0.9, "temperature": 1.0}]
+
+
+@pytest.mark.parametrize("cfg", DRAW_CFGS, ids=["random", "random_T0.7", "top_k5", "top_p0.9"])
 def test_scalar_tail_draws_equal_oracle_on_identical_uniforms(harness, tmp_path, golden_dir, cfg):
     """Stochastic samplers: same Philox uniforms (seed, global layout index, step, position) as the oracle's inverse-CDF
     rule, i.e. as the wave-per-token kernel: token for token, except where fp32 rounding moves a CDF edge across u."""
@@ -200,7 +194,10 @@ def test_scalar_tail_gumbel_equals_oracle_on_identical_words(harness, tmp_path, 
     assert bad <= 2, f"{bad}/{total}"
 
 
-@pytest.mark.parametrize("variant", ["no_noise", "shared_across_classes", "before_division", "draw_word_reused"])
+WRONG_NOISE = ["no_noise", "shared_across_classes", "before_division", "draw_word_reused"]
+
+
+@pytest.mark.parametrize("variant", WRONG_NOISE)
 def test_scalar_tail_gumbel_parity_rejects_wrong_noise(harness, tmp_path, golden_dir, variant):
     """The parity check above is not vacuous: against an oracle whose noise is missing, shared by the classes of a token
     (it cancels in the softmax), added before the temperature division, or taken from the draw's own Philox block, the
@@ -305,3 +302,22 @@ def test_live_class_form_needs_the_temperature_bound(harness, tmp_path, golden_d
     print(f"[host live-class form, T=10] oracle draws on dead classes {dead_drawn}/{total}; tokens differing {bad}/{total}")
     assert dead_drawn >= 0.002 * total     # the reference's distribution does put >= 0.35 % of its mass there (docstring)
     assert bad >= dead_drawn               # ... and the live-class form can follow none of those draws
+
+
+def test_scalar_tail_under_address_and_undefined_sanitizers(tmp_path, golden_dir):
+    """every case above once more on the ASan + UBSan build of the same program: the tail indexes the token's logits row, its
+    working storage (aliased onto that row or separate) and the sub-vocabulary slots by formulas the kernel shares; a read or
+    write past any of them, or signed overflow in the index arithmetic, ends the run with a non-zero code"""
+    exe = HB.host_program("cpu_post_token_check", sanitize=True, extra=("-Wextra",))
+    for f64 in (True, False):
+        test_scalar_tail_greedy_equals_reference_tokens(exe, tmp_path, golden_dir, f64)
+    for cfg in DRAW_CFGS:
+        test_scalar_tail_draws_equal_oracle_on_identical_uniforms(exe, tmp_path, golden_dir, cfg)
+    test_scalar_tail_gumbel_support_and_determinism(exe, tmp_path, golden_dir)
+    for temperature in (1.0, 0.7):
+        test_scalar_tail_gumbel_equals_oracle_on_identical_words(exe, tmp_path, golden_dir, temperature)
+    for variant in WRONG_NOISE:
+        test_scalar_tail_gumbel_parity_rejects_wrong_noise(exe, tmp_path, golden_dir, variant)
+    for ds in ("rico25", "publaynet"):
+        test_scalar_tail_parameter_edges(exe, tmp_path, golden_dir, ds)
+    test_live_class_form_needs_the_temperature_bound(exe, tmp_path, golden_dir)

@@ -5,42 +5,33 @@ tests/cpu_refine_check.cpp, walking workgroups and threads like the kernel) agai
 host function the product path used: BIT FOR BIT, compared as int32 (so that -0.0 under a negative weight counts).  Rico25
 and PubLayNet; uniform / negative / gaussian tables; weights 3.0, 0.1, -3.0; every output misalignment a slice of a larger
 buffer can have; the (1,S) -> B broadcast; int32 and int64 ids; the out-of-range ids -1 and C.  The same program built with
--fsanitize=address,undefined runs the same cases.  Also: the export refusing bad arguments, the kernels' resource report
+ASan + UBSan (tests/_hostbuild.py) runs the same cases.  Also: the export refusing bad arguments, the kernels' resource report
 (no scratch, no atomics, 16-byte stores), and the Python functions raising without a GPU."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import _hostbuild as HB
 from _stub_tokenizer import StubTokenizer
 from oracle import spec as SP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpu_refine_check.cpp")
 MODES = ("uniform", "negative", "gaussian")
 WEIGHTS = (3.0, 0.1, -3.0)
 
 
-def _build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, SRC, "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+@pytest.fixture(scope="module")
+def host_exe():
+    return HB.host_program("cpu_refine_check")
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("refine"), "cpu_refine_check", ["-O2"])
-
-
-@pytest.fixture(scope="module")
-def san_exe(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("refine_san"), "cpu_refine_check_san",
-                  ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+def san_exe():
+    return HB.host_program("cpu_refine_check", sanitize=True)
 
 
 def host_run(exe, tmp_path, seq, table, weight, B, mis=0):
@@ -48,19 +39,11 @@ def host_run(exe, tmp_path, seq, table, weight, B, mis=0):
     seq = np.ascontiguousarray(seq)
     assert seq.dtype in (np.int32, np.int64) and seq.ndim == 2
     Cn, S = table.shape[0], seq.shape[1]
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([seq.dtype == np.int64, seq.shape[0], B, S, Cn, mis], np.int32).tobytes())
-        f.write(np.float32(weight).tobytes())
-        f.write(seq.tobytes())
-        f.write(np.ascontiguousarray(table, np.float32).tobytes())
-    if outp.exists():
-        outp.unlink()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1")
-    rc = subprocess.run([exe, str(inp), str(outp)], env=env).returncode
+    rc, raw = HB.run_host_io(exe, tmp_path, np.array([seq.dtype == np.int64, seq.shape[0], B, S, Cn, mis], np.int32).tobytes() +
+                             np.float32(weight).tobytes() + seq.tobytes() + np.ascontiguousarray(table, np.float32).tobytes())
     if rc != 0:
         return rc, None, None
-    raw = np.fromfile(outp, np.uint8)
+    raw = np.frombuffer(raw, np.uint8)
     return rc, int(raw[:4].view(np.int32)[0]), raw[4:].view(np.float32).reshape(B, Cn, S)
 
 
@@ -163,7 +146,7 @@ def test_host_build_geometry_edges(host_exe, tmp_path):
 
 
 def test_host_build_under_address_and_undefined_sanitizers(san_exe, tmp_path):
-    """the same cases, the stand-alone program built with -fsanitize=address,undefined: a read past the ids or the table, a
+    """the same cases, the stand-alone program as the ASan + UBSan build: a read past the ids or the table, a
     write past the output, signed overflow or a misaligned access in the index arithmetic ends the run with a non-zero code"""
     _cases(san_exe, tmp_path)
     _geometry_cases(san_exe, tmp_path)
@@ -192,16 +175,8 @@ def test_cabi_export_and_refuses_bad_arguments():
     assert call(B=0, B_seq=0, seq=None, out=None) == 0 and call(B=0, B_seq=1, out=None, err=None) == 0
 
 
-def test_refine_kernels_use_no_scratch_no_atomics_and_store_16_bytes(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    asm_path = tmp_path / "refine.s"
-    out = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o",
-                          str(asm_path), os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_refine.hip"),
-                          "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900).stdout
-    assert "error:" not in out, out
+def test_refine_kernels_use_no_scratch_no_atomics_and_store_16_bytes():
+    asm, out, _ = HB.kernel_asm("kernels_refine.hip", resource_report=True)
     seen = 0
     for blk in re.split(r"Function Name: ", out)[1:]:
         if "refinement_prior_k" not in blk.split()[0]:
@@ -213,7 +188,6 @@ def test_refine_kernels_use_no_scratch_no_atomics_and_store_16_bytes(tmp_path):
         assert get(r"LDS Size \[bytes/block\]: (\d+)") <= 4096, blk       # kMaxStaged ids, or none
         assert get(r"Occupancy \[waves/SIMD\]: (\d+)") == 8, blk
     assert seen == 2
-    asm = asm_path.read_text()
     bodies = re.findall(r"^(\S*refinement_prior_k\S*):[^\n]*$(.*?)^\.Lfunc_end", asm, flags=re.S | re.M)
     assert len(bodies) == 2
     for name, body in bodies:

@@ -11,11 +11,12 @@ arguments."""
 import ctypes as C
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
+
+import _hostbuild as HB
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,11 +39,8 @@ def fx(golden_dir):
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("relation_violation") / "cpu_relation_detect_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpu_relation_detect_check.cpp"),
-                    "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def host_exe():
+    return HB.host_program("cpu_relation_detect_check")
 
 
 def csr_of(y, edge_index, edge_attr, batch):
@@ -58,14 +56,12 @@ def csr_of(y, edge_index, edge_attr, batch):
 def host_run(exe, tmp_path, box, y, edge_index, edge_attr, batch):
     """-> (exit code, per-edge (E,4) int32 in edge_index's order, scores (n_graph,) float32)"""
     n_graph, off, src, dst, attr, first, order = csr_of(y, edge_index, edge_attr, batch)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([box.dtype == np.float64, len(box), len(y), n_graph, len(attr)], np.int32).tobytes())
-        for a, dt in ((box, box.dtype), (y == 0, np.uint8), (off, np.int32), (src, np.int32), (dst, np.int32), (attr, np.int32),
-                      (first, np.int64)):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
-    rc = subprocess.run([exe, str(inp), str(outp)]).returncode
-    raw = np.fromfile(outp, np.uint8)
+    payload = np.array([box.dtype == np.float64, len(box), len(y), n_graph, len(attr)], np.int32).tobytes()
+    for a, dt in ((box, box.dtype), (y == 0, np.uint8), (off, np.int32), (src, np.int32), (dst, np.int32), (attr, np.int32),
+                  (first, np.int64)):
+        payload += np.ascontiguousarray(a, dt).tobytes()
+    rc, raw = HB.run_host_io(exe, tmp_path, payload)
+    raw = np.frombuffer(raw, np.uint8)
     E = len(attr)
     edge_csr = raw[:16 * E].view(np.int32).reshape(E, 4)
     edge = np.empty_like(edge_csr)
@@ -102,6 +98,15 @@ def test_host_build_refuses_a_row_beyond_the_boxes(host_exe, tmp_path, fx):
     box, y, ei, ea, batch = G.load_inputs(fx)["edge"]["f32"]
     rc, _, _ = host_run(host_exe, tmp_path, box[:-1], y, ei, ea, batch)   # the last node has edges
     assert int(ei.max()) == len(box) - 1 and rc == 3
+
+
+def test_host_build_under_address_and_undefined_sanitizers(tmp_path, fx):
+    """every host-build case above on the ASan + UBSan build: boxes, canvas flags and the CSR arrays are exact-size allocations
+    (the two `empty` sets write zero edges: nothing is handed to fwrite there)"""
+    exe = HB.host_program("cpu_relation_detect_check", sanitize=True)
+    for name, prec in CASES:
+        test_host_build_equals_the_reference_bit_for_bit(exe, tmp_path, fx, name, prec)
+    test_host_build_refuses_a_row_beyond_the_boxes(exe, tmp_path, fx)
 
 
 def test_handmade_inputs_are_reproducible_and_hit_their_boundaries(fx):

@@ -12,12 +12,12 @@ import ctypes as C
 import importlib.util
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
+
+import _hostbuild as HB
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -39,28 +39,21 @@ def fx(golden_dir):
 
 
 @pytest.fixture(scope="module")
-def host_exe(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("render") / "cpu_render_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpu_render_check.cpp"),
-                    "-o", str(exe)], check=True, cwd=ROOT)
-    return str(exe)
+def host_exe():
+    return HB.host_program("cpu_render_check")
 
 
 def host_run(exe, tmp_path, bbox, label, mask, colors, canvas, cols=1, pad=0):
     """-> (exit code, error word, (GH,GW,3) uint8)"""
     B, S = mask.shape
     H, W = (int(v) for v in canvas)
-    inp, outp = tmp_path / "in.bin", tmp_path / "out.bin"
-    with open(inp, "wb") as f:
-        f.write(np.array([bbox.dtype == np.float64, B, S, len(colors), H, W, cols, pad], np.int32).tobytes())
-        for a, dt in ((bbox, bbox.dtype), (label, np.int64), (mask, np.uint8), (colors, np.uint8)):
-            f.write(np.ascontiguousarray(a, dt).tobytes())
-    if outp.exists():
-        outp.unlink()
-    rc = subprocess.run([exe, str(inp), str(outp)]).returncode
+    payload = np.array([bbox.dtype == np.float64, B, S, len(colors), H, W, cols, pad], np.int32).tobytes()
+    for a, dt in ((bbox, bbox.dtype), (label, np.int64), (mask, np.uint8), (colors, np.uint8)):
+        payload += np.ascontiguousarray(a, dt).tobytes()
+    rc, raw = HB.run_host_io(exe, tmp_path, payload)
     if rc != 0:
         return rc, None, None
-    raw = np.fromfile(outp, np.uint8)
+    raw = np.frombuffer(raw, np.uint8)
     GH, GW = mosaic_shape(B, H, W, cols, pad)
     return rc, int(raw[:4].view(np.int32)[0]), raw[4:].reshape(GH, GW, 3)
 
@@ -174,6 +167,16 @@ def test_host_error_word_and_what_is_still_drawn(host_exe, tmp_path, fx):
     assert host_run(host_exe, tmp_path, z((1, 2, 4), np.float32), z((1, 2), np.int64), z((1, 2), bool), colors, (0, 40))[0] == 2
 
 
+def test_host_build_under_address_and_undefined_sanitizers(tmp_path, fx):
+    """every host-build case above on the ASan + UBSan build: rank_of places each drawn element in exact-size arrays of S slots,
+    and every pixel is written through tile_origin's index into an exact-size mosaic"""
+    exe = HB.host_program("cpu_render_check", sanitize=True)
+    for name in SETS:
+        test_host_build_equals_the_reference_byte_for_byte(exe, tmp_path, fx, name)
+    test_host_mosaic_equals_numpy_assembly_of_the_fixture_images(exe, tmp_path, fx)
+    test_host_error_word_and_what_is_still_drawn(exe, tmp_path, fx)
+
+
 def test_handmade_inputs_are_reproducible_and_hit_what_they_aim_at(fx):
     inp = G.inputs()
     loaded = G.load_inputs(fx)
@@ -271,17 +274,10 @@ def test_cabi_exports_and_refuses_bad_arguments():
     assert lib.ldm_render_grid_shape(1, 60, 40, 1, 0, None, C.byref(gw)) == -1
 
 
-def test_render_kernels_use_no_scratch(tmp_path):
+def test_render_kernels_use_no_scratch():
     """from the compiler's resource report (what tools/kernel_resources.py prints): both instances of render_layouts_k, no
     scratch, no spills, and the LDS of the ranked list only"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = subprocess.run([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", "-o",
-                          str(tmp_path / "render.s"), os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_render.hip"),
-                          "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900).stdout
-    assert "error:" not in out, out
+    _, out, _ = HB.kernel_asm("kernels_render.hip", resource_report=True)
     blocks = re.split(r"Function Name: ", out)[1:]
     seen = 0
     for blk in blocks:

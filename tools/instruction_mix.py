@@ -19,7 +19,6 @@ sampler loops (top-k / top-p order walk) are counted with zero trips, i.e. the t
 import collections
 import os
 import re
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,9 +191,10 @@ def main():
         asm = sys.argv[sys.argv.index("--asm") + 1]
     else:
         asm = "/tmp/ldm_stack_mix.s"
-        src = os.path.join(ROOT, "layout_dm_amd", "csrc", "kernels_stack.hip")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only",
-                        "-S", "-o", asm, src, "-Wno-unused-function"], check=True, stderr=subprocess.DEVNULL)
+        sys.path.insert(0, ROOT)
+        from layout_dm_amd import build
+
+        build.device_asm("kernels_stack.hip", asm)
     phases, total = mix(asm)
     valu = [k for k in CLASSES if k.startswith("valu")]
     print("# dynamic instruction mix of stack_stream_k<false,2> per WAVEFRONT and reverse step (sampling=random), from the gfx950")

@@ -11,6 +11,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from layout_dm_amd import build  # noqa: E402
 
 
 def main():
@@ -21,13 +23,11 @@ def main():
         asm = argv[i + 1]
         del argv[i:i + 2]
     args = [a for a in argv if not a.startswith("--")]
-    src = os.path.join(ROOT, "layout_dm_amd", "csrc", args[0])
     flt = args[1] if len(args) > 1 else ""
-    cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S",
-           "-o", asm, src, "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-    if "error:" in out:
-        print(out)
+    try:
+        _, out = build.device_asm(args[0], asm, resource_report=True)
+    except RuntimeError as e:
+        print(e)
         sys.exit(1)
     cur = None
     rows = []
