@@ -175,6 +175,30 @@ int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm_cond* cond
                     uint64_t seed, uint64_t first_layout, int B, int32_t* d_intermediates, int use_graph,
                     void* stream);
 
+/* ---- scoring GIVEN layouts: held-out loss / variational bound ---------------------------------
+ * ConstrainedMaskAndReplaceDiffusion.forward (constrained.py:232-333) / VanillaMaskAndReplaceDiffusion.forward
+ * (vanilla.py:160-240) as evaluation of a trained model: no gradients, nothing is written to the handle's weights.
+ * Every call checks its tokens on the device and reads the result back before it returns (one stream synchronisation):
+ * a token outside [0, C), a [MASK] in x_0, or a token that is not of its position's sub-vocabulary fails with -6.
+ * t outside [0, n_step) fails with -1. */
+/* x_t ~ q(x_t | x_0) (q_sample, constrained.py:223-230): (B,S) int32 -> (B,S) int32.  Inverse CDF on one Philox4x32-10
+ * uniform per token, keyed by (seed, first_layout + b, t, position), over the reference's exp(q_pred) — not the
+ * reference's Gumbel-argmax stream on torch's generator, which cannot be reproduced.  Independent of how a batch is cut. */
+int ldm_q_sample(ldm_handle* h, const int32_t* d_x0, int t, uint64_t seed, uint64_t first_layout, int B, int32_t* d_xt,
+                 void* stream);
+/* The bound's terms of timestep t for given x_0, x_t (B,S) int32 and the denoiser's logits (B,S,C) of (x_t, t).
+ * d_sums (B,4) float64: per layout the SUMS over its tokens of kl (base.py:117-119 of the two posteriors), decoder nll
+ * (util.py:30-31), the auxiliary kl (constrained.py:317-319) and the number of tokens whose argmax log_x0_recon is x_0;
+ * the 1 / S of mean_except_batch, the t == 0 selection and the loss weights are the caller's.  Fixed summation order
+ * (lane tree per token in float32, then positions left to right in float64), no atomics: the bits repeat.
+ * d_tok: NULL or (3,B,S) float32 per-token kl, nll, aux. */
+int ldm_vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, int t, int B,
+                 double* d_sums, float* d_tok, void* stream);
+/* ldm_q_sample (d_xt == NULL; else the given state) -> the denoiser pass of the handle's numerics mode -> ldm_vb_terms,
+ * chunk by chunk through the handle's own workspace. */
+int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, uint64_t seed, uint64_t first_layout,
+                int B, double* d_sums, void* stream);
+
 /* ---- near-tie report of deterministic decoding (ABI 4; tie_abs: ABI 5) ------------------------
  * north star: "token indices bit-exact under greedy/argmax decoding".  LDM_PREC_FAST_F16's logits carry an error that
  * depends on the checkpoint (3e-4 of max |logit| on the reference's init, 1e-3 on wider weights, more once attention rows

@@ -44,6 +44,8 @@ EXPORTS = (
     # coordinate bins from raw boxes (bound in layout_dm_amd/clustering.py)
     "ldm_cluster_workspace_bytes", "ldm_cluster_sort", "ldm_kmeans1d_fit", "ldm_kmeans1d_lloyd", "ldm_percentile_fit",
     "ldm_nearest_centre", "ldm_dev_cluster_stages",
+    # scoring given layouts (Engine.q_sample / vb_terms / vb_step)
+    "ldm_q_sample", "ldm_vb_terms", "ldm_vb_step",
 )
 
 
@@ -156,6 +158,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_percentile_fit.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, sz, vp]
     lib.ldm_nearest_centre.argtypes = [vp, i64, vp, i32, i32, vp, vp]
     lib.ldm_dev_cluster_stages.argtypes = [vp, i64, i32, u64, i32, i32, i32, f64] + [vp] * 13 + [sz, vp, vp]
+    lib.ldm_q_sample.argtypes = [vp, vp, i32, u64, u64, i32, vp, vp]
+    lib.ldm_vb_terms.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.ldm_vb_step.argtypes = [vp, vp, vp, i32, u64, u64, i32, vp, vp]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int
@@ -355,6 +360,52 @@ class Engine:
                     "ldm_sample_tokens")
         if keep:
             torch.cuda.current_stream(self.device).synchronize()
+        return out
+
+    # ------------------------------------------------------------------ scoring given layouts
+    def _check_tokens(self, rc: int, what: str):
+        if rc == -6:   # a token the kernels refused (include/ldm_hip.h): the reference's index_to_log_onehot asserts
+            raise ValueError(f"{what}: {self.lib.ldm_last_error(self._h).decode()}")
+        self._check(rc, what)
+
+    def q_sample(self, x0: torch.Tensor, t: int, seed: int = 0, first_layout: int = 0) -> torch.Tensor:
+        """x_t ~ q(x_t | x_0) (constrained.py:223-230): (B,S) ids -> (B,S) int32 on the device.  One Philox uniform per
+        token keyed by (seed, first_layout + b, t, position): the tokens do not depend on how a batch is cut over calls."""
+        x0 = self._tok(x0)
+        out = torch.empty_like(x0)
+        self._check_tokens(self.lib.ldm_q_sample(self._h, x0.data_ptr(), int(t), int(seed), int(first_layout), x0.shape[0],
+                                                 out.data_ptr(), _stream_ptr(self.device)), "ldm_q_sample")
+        return out
+
+    def vb_terms(self, logits: torch.Tensor, x0: torch.Tensor, xt: torch.Tensor, t: int, per_token: bool = False):
+        """The bound's terms of timestep t from the denoiser's logits (B,S,C) of (xt, t): (B,4) float64 per-layout SUMS
+        over the tokens of kl, decoder nll, auxiliary kl and x_0 hits (include/ldm_hip.h ldm_vb_terms); per_token: also the
+        (3,B,S) float32 kl / nll / aux of every token."""
+        x0, xt = self._tok(x0), self._tok(xt)
+        B = x0.shape[0]
+        assert xt.shape == x0.shape == (B, self.S) and tuple(logits.shape) == (B, self.S, self.C)
+        logits = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        sums = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        tok = torch.empty((3, B, self.S), dtype=torch.float32, device=self.device) if per_token else None
+        self._check_tokens(self.lib.ldm_vb_terms(self._h, logits.data_ptr(), x0.data_ptr(), xt.data_ptr(), int(t), B,
+                                                 sums.data_ptr(), tok.data_ptr() if per_token else None,
+                                                 _stream_ptr(self.device)), "ldm_vb_terms")
+        return (sums, tok) if per_token else sums
+
+    def vb_step(self, x0: torch.Tensor, t: int, xt: Optional[torch.Tensor] = None, seed: int = 0, first_layout: int = 0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """q_sample (xt None; else the given state) -> this engine's denoiser pass -> vb_terms: (B,4) float64 sums."""
+        x0 = self._tok(x0)
+        B = x0.shape[0]
+        if xt is not None:
+            xt = self._tok(xt)
+            assert xt.shape == x0.shape
+        if out is None:
+            out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        assert out.shape == (B, 4) and out.dtype == torch.float64 and out.is_contiguous() and out.device == self.device
+        self._check_tokens(self.lib.ldm_vb_step(self._h, x0.data_ptr(), xt.data_ptr() if xt is not None else None, int(t),
+                                                int(seed), int(first_layout), B, out.data_ptr(), _stream_ptr(self.device)),
+                           "ldm_vb_step")
         return out
 
     # ------------------------------------------------------------------ hot path

@@ -3,6 +3,7 @@
 //   ldm_api.cpp      lifecycle, parity hooks, result packaging, near-tie report, introspection
 //   ldm_weights.cpp  checkpoint upload, fp16 / LDS weight images, parameter tables (ldm_load_weight / ldm_finalize_weights)
 //   ldm_denoise.cpp  the launch sequence of one denoiser pass over a chunk, per numerics mode
+//   ldm_vb_api.cpp   scoring given layouts: forward noising draw, variational-bound terms (ldm_q_sample / ldm_vb_terms / ldm_vb_step)
 //   ldm_loop.cpp     the hot path: one reverse step, the one-launch loop, the per-lane hipGraph loop (ldm_sample_step / _loop)
 #pragma once
 #include "../../include/ldm_hip.h"
@@ -233,6 +234,7 @@ struct ldm_handle {
   float* st_rel_centres = nullptr;      // (4, n_bin)
   int32_t *tok_a = nullptr, *tok_b = nullptr;  // loop state ping-pong (max_batch)
   uint64_t* rng = nullptr;                      // device {seed, first_layout}
+  int32_t* vb_err = nullptr;                    // error word of the scoring entry points (ldm_vb_api.cpp), allocated on first use
   // profiling
   bool profiling = false;
   std::vector<ProfEntry> prof;

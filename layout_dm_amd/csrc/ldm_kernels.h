@@ -420,6 +420,26 @@ enum ScheduleRow { kLogAt = 0, kLogBt, kLogCt, kLogCumAt, kLogCumBt, kLogCumCt, 
 void launch_posterior_sample(const PostArgs& p, hipStream_t st);
 void launch_set_rng(uint64_t* rng, uint64_t seed, uint64_t first_layout, hipStream_t st);
 
+// ---- scoring given layouts (kernels_vb.hip; arithmetic: ldm_vb_core.h); arguments checked by the C-ABI (ldm_vb_api.cpp)
+struct VbArgs {
+  const int32_t* x0;       // [B, S]
+  const int32_t* xt;       // [B, S] (vb_terms)
+  int32_t* xt_out;         // [B, S] (q_sample)
+  const float* logits;     // [B S, ldl] (vb_terms; cols >= n_class - 1 ignored)
+  int ldl;
+  const float* sched;      // device [8][n_attr][T+1] schedule buffers (ScheduleRow)
+  int T, t;
+  uint64_t seed, first_layout;   // Philox key / global index of layout 0 (q_sample)
+  int f32_lse;             // 1: fp32 log-softmax and hardware exp / log (fast numerics mode)
+  int B, S;
+  VocabTables v;
+  double* sums;            // [B, 4] kl, nll, aux, hits: sums over the layout's tokens
+  float* tok_out;          // (3, B, S) per-token kl, nll, aux, or nullptr
+  int32_t* err;            // error word (ldm_vb_core.h kErr*), OR-ed into
+};
+void launch_q_sample(const VbArgs& p, hipStream_t st);
+void launch_vb_terms(const VbArgs& p, hipStream_t st);
+
 // ---- FID feature extractor (kernels_fid.hip): FIDNetV3.extract_features, trainer/fid/model.py:123-164 -------------
 struct FidLayer {            // nn.TransformerEncoderLayer(256, 4, 128), weights TRANSPOSED to [K][N]
   const float *in_wt, *in_b;     // [256][768], [768]

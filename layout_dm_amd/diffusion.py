@@ -14,6 +14,7 @@ import itertools
 import logging
 from typing import Dict, List, Optional, Union
 
+import numpy as np
 import torch
 
 from .binding import Engine
@@ -84,7 +85,7 @@ class HipMaskAndReplaceDiffusion:
                  d_model: int = 464, n_head: int = 8, d_ff: int = 1856, n_layer: int = 4,
                  num_timesteps: int = 100, precision: str = "exact", max_batch: int = 512, chunk: int = 0,
                  device: Optional[int] = None, use_graph: bool = True, q_type: str = "constrained", lanes: int = 0,
-                 verifier: str = "split"):
+                 verifier: str = "split", auxiliary_loss_weight: float = 1e-1):
         # q_type: Q_TYPES of models/layoutdm.py:20-23 — "constrained" (constrained.py) or "vanilla" (vanilla.py)
         # precision "fast_verified": the fp16 engine for every sampler, plus an exact (fp32) engine of the same weights
         # that re-decides the near-tie layouts of DETERMINISTIC decoding (layout_dm_amd/verified.py): greedy tokens are
@@ -135,6 +136,12 @@ class HipMaskAndReplaceDiffusion:
         self.use_graph = use_graph
         self.mask_id = self.engine.mask_id
         self.pad_id = self.engine.pad_id
+        # held-out loss (loss / evaluate): base.py:43,99,106-107.  The two history buffers of the checkpoint stay on the host
+        # (time_weights reads them; nothing here writes them)
+        self.auxiliary_loss_weight = float(auxiliary_loss_weight)
+        self.adaptive_auxiliary_loss = True
+        self.Lt_history: Optional[torch.Tensor] = None
+        self.Lt_count: Optional[torch.Tensor] = None
 
     # -- nn.Module-ish surface used by the reference's callers --------------------------------
     @property
@@ -191,6 +198,9 @@ class HipMaskAndReplaceDiffusion:
         self.verifier_check["verifier"] = "exact (fallback)"
 
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
+        for k, v in state_dict.items():                         # (keys with or without 'model.module.')
+            if k.rsplit(".", 1)[-1] in ("Lt_history", "Lt_count"):
+                setattr(self, k.rsplit(".", 1)[-1], torch.as_tensor(v).detach().to("cpu", torch.float32).reshape(-1).clone())
         if self.verified is not None:
             self.verified = self._v_fast                        # (auto may have switched to the mixed / the reference-precision engine before)
             self.engine = self.verified.fast
@@ -381,3 +391,147 @@ class HipMaskAndReplaceDiffusion:
         if return_device_tensor:
             return out
         return out.long().cpu()
+
+    # -- scoring given layouts: forward() as evaluation (constrained.py:232-333, vanilla.py:160-240) --------------------
+    def _draw_seed(self, seed: Optional[int]) -> int:
+        return int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+
+    def _cut(self, B: int):
+        eng, off = self.engine, 0
+        for n in batch_cuts(B, eng.max_batch, eng.batch_round):
+            yield off, n
+            off += n
+
+    def time_weights(self) -> torch.Tensor:
+        """pt_all of sample_time("importance") (base.py:179-198): (T,) float32 on the host from the checkpoint's Lt_history /
+        Lt_count, or 1 / T everywhere while some timestep has been visited 10 times or fewer (or the checkpoint has no history)."""
+        T = self.num_timesteps
+        if not self._has_history():
+            return torch.from_numpy(np.full(T, np.float32(1) / np.float32(T), np.float32))
+        # float32 like the reference's buffers: weight of t = sqrt(running mean of L_t^2), floored; t = 0 (the decoder term,
+        # on another scale than the kl terms) is sampled as often as t = 1; normalised to probabilities
+        w = np.sqrt(self.Lt_history.numpy().astype(np.float32) + np.float32(1e-10)) + np.float32(1e-4)
+        w[0] = w[1]
+        return torch.from_numpy(w / w.sum(dtype=np.float32))
+
+    def _has_history(self) -> bool:
+        """every timestep visited more than 10 times during training (base.py:181), so that Lt_history means something"""
+        return self.Lt_history is not None and self.Lt_count is not None and bool((self.Lt_count.numpy() > 10).all())
+
+    def sample_time(self, b: int):
+        """(t (b,) int64, pt (b,) float32) on the host like base.py:179-198 draws them (torch's global CPU generator)."""
+        pt_all = self.time_weights()
+        if not self._has_history():
+            t = torch.randint(0, self.num_timesteps, (b,)).long()
+        else:
+            t = torch.multinomial(pt_all, num_samples=b, replacement=True)
+        return t, pt_all.gather(0, t)
+
+    @torch.no_grad()
+    def q_sample(self, x0: torch.Tensor, t: int, seed: int = 0, first_layout: int = 0) -> torch.Tensor:
+        """x_t ~ q(x_t | x_0) for the whole batch at one t (Engine.q_sample), (B,S) int32 on the device."""
+        eng = self.engine
+        x0 = eng._tok(torch.as_tensor(x0))
+        parts = [eng.q_sample(x0[off:off + n], t, seed, first_layout + off) for off, n in self._cut(x0.shape[0])]
+        return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+    @torch.no_grad()
+    def vb_terms(self, x0: torch.Tensor, t: int, x_t: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                 first_layout: int = 0) -> Dict[str, torch.Tensor]:
+        """The variational bound's terms of ONE timestep for given layouts x0 (B,S): per-layout float64 tensors on the device,
+        every value a mean over the layout's S tokens (mean_except_batch) —
+            kl           KL(q(x_{t-1} | x_t, x_0) || p_theta(x_{t-1} | x_t))       constrained.py:289-299
+            decoder_nll  -log p_theta(x_0 | x_t)                                   constrained.py:301-302
+            kl_aux       KL(x_0 || p_theta(x_0 | x_t)) over the non-[MASK] classes   constrained.py:317-321
+            x0_acc       share of tokens whose most likely x_0 is the true one     constrained.py:269-277
+        x_t: the noised state to score at, or None: drawn, x_t ~ q(x_t | x_0), with a Philox stream keyed by (seed,
+        first_layout + b, t, position) — not the reference's Gumbel-argmax stream on torch's generator, which cannot be
+        reproduced; seed None draws the key from torch's global CPU generator.  Evaluation only: no gradient exists."""
+        eng = self.engine
+        x0 = eng._tok(torch.as_tensor(x0))
+        if x_t is not None:
+            x_t = eng._tok(torch.as_tensor(x_t))
+            assert x_t.shape == x0.shape
+        seed = 0 if x_t is not None else self._draw_seed(seed)
+        sums = torch.empty((x0.shape[0], 4), dtype=torch.float64, device=eng.device)
+        self._vb_sums(x0, t, x_t, seed, first_layout, sums)
+        mean = sums / eng.S                                     # the 1 / S of mean_except_batch (one elementwise launch)
+        return {"kl": mean[:, 0], "decoder_nll": mean[:, 1], "kl_aux": mean[:, 2], "x0_acc": mean[:, 3]}
+
+    def _vb_sums(self, x0, t, x_t, seed, first_layout, out) -> None:
+        """Engine.vb_step of a staged (B,S) int32 device batch, cut by batch_cuts, into out (B,4) float64 on the device."""
+        eng = self.engine
+        for off, n in self._cut(x0.shape[0]):
+            eng.vb_step(x0[off:off + n], t, xt=None if x_t is None else x_t[off:off + n], seed=seed,
+                        first_layout=first_layout + off, out=out[off:off + n])
+
+    @torch.no_grad()
+    def elbo(self, x0: torch.Tensor, n_draws: int = 1, seed: Optional[int] = None, first_layout: int = 0) -> torch.Tensor:
+        """Per-layout variational bound on -log p(x_0) in nats per token, (B,) float64 on the device: the sum over t = 0 .. T - 1
+        of the reference's kl_loss term (constrained.py:304-305: decoder_nll at t = 0, kl otherwise) at one drawn x_t per t,
+        averaged over n_draws independent draws (Philox keys seed, seed + 1, ...).  The whole batch goes through each t: T
+        denoiser passes per draw.  The reference's bound carries no prior term L_T = KL(q(x_T | x_0) || p(x_T)), so neither
+        does this one (L_T does not depend on the model: it shifts every checkpoint's bound alike).  A stochastic estimate: compare checkpoints or layouts under the same seed."""
+        if n_draws < 1:
+            raise ValueError("n_draws must be >= 1")
+        seed = self._draw_seed(seed)
+        eng, T = self.engine, self.num_timesteps
+        x0 = eng._tok(torch.as_tensor(x0))                       # staged once for all T passes
+        sums = torch.empty((int(n_draws) * T, x0.shape[0], 4), dtype=torch.float64, device=eng.device)
+        for d in range(int(n_draws)):
+            for t in range(T):
+                self._vb_sums(x0, t, None, seed + d, first_layout, sums[d * T + t])
+        # one elementwise launch for the token means (the values vb_terms returns), then the T terms of a draw are added on
+        # the host in their order, t = 0 first: B x T float64 additions, exactly the sum of the vb_terms calls
+        mean = (sums / eng.S).cpu().numpy()
+        total = np.zeros(x0.shape[0])
+        for i in range(mean.shape[0]):
+            total = total + mean[i, :, 1 if i % T == 0 else 0]
+        if n_draws > 1:
+            total = total / int(n_draws)
+        return torch.from_numpy(total).to(eng.device)
+
+    @torch.no_grad()
+    def loss(self, x0: torch.Tensor, t: Optional[torch.Tensor] = None, pt: Optional[torch.Tensor] = None,
+             seed: Optional[int] = None, x_t: Optional[torch.Tensor] = None, first_layout: int = 0) -> Dict[str, torch.Tensor]:
+        """The reference's losses of one batch, {"kl_loss", "aux_loss"} (constrained.py:304-330 with adaptive_auxiliary_loss; no
+        "aux_loss" when auxiliary_loss_weight is 0), as float64 scalars on the host.  t (B,) per-layout timesteps and pt their
+        sampling probabilities: None -> sample_time() / time_weights()[t].  x_t: given states (B,S), else drawn per layout at
+        its own t (vb_terms' stream: a layout's draw depends on seed, its global index and its t alone).  Layouts are grouped
+        by t on the host, one denoiser pass per distinct value.  Cost: ldm_q_sample takes ONE t per call, so with drawn
+        x_t the whole batch is noised once per distinct t and the group picked out of it (a batch of 64 at ~45 distinct t:
+        45 small draw launches and 45 vb_step calls, each with its error-word read-back) — evaluation batches, not a hot path."""
+        eng = self.engine
+        x0 = eng._tok(torch.as_tensor(x0))
+        B, T = x0.shape[0], self.num_timesteps
+        if t is None:
+            t, pt_drawn = self.sample_time(B)
+            pt = pt_drawn if pt is None else pt
+        t = torch.as_tensor(t).to("cpu", torch.int64).reshape(-1)
+        if t.numel() != B or int(t.min()) < 0 or int(t.max()) >= T:
+            raise ValueError(f"t must be ({B},) timesteps in [0, {T})")
+        pt = self.time_weights().gather(0, t) if pt is None else torch.as_tensor(pt).to("cpu").reshape(-1)
+        if x_t is not None:
+            x_t = eng._tok(torch.as_tensor(x_t))
+        seed = 0 if x_t is not None else self._draw_seed(seed)
+        sums = torch.empty((B, 4), dtype=torch.float64)
+        for tv in sorted(set(t.tolist())):
+            idx = (t == tv).nonzero().reshape(-1)
+            idx_d = idx.to(eng.device)
+            xt_all = x_t if x_t is not None else self.q_sample(x0, tv, seed, first_layout)
+            x0_g, xt_g = x0.index_select(0, idx_d), xt_all.index_select(0, idx_d)
+            part = torch.empty((idx.numel(), 4), dtype=torch.float64, device=eng.device)
+            for off, n in self._cut(idx.numel()):
+                eng.vb_step(x0_g[off:off + n], tv, xt=xt_g[off:off + n], out=part[off:off + n])
+            sums[idx] = part.cpu()
+        # B scalars from here on, on the host in float64
+        mean = sums.numpy() / eng.S
+        tn, ptn = t.numpy(), pt.double().numpy()
+        first = tn == 0
+        kl_loss = np.where(first, mean[:, 1], mean[:, 0])                                # constrained.py:304-305
+        out = {"kl_loss": torch.tensor(float((kl_loss / ptn).mean()), dtype=torch.float64)}
+        if self.auxiliary_loss_weight != 0:
+            kl_aux_loss = np.where(first, mean[:, 1], mean[:, 2])                        # l.322
+            w = (1 - tn / T) + 1.0 if self.adaptive_auxiliary_loss else 1.0              # l.323-326
+            out["aux_loss"] = torch.tensor(float((w * self.auxiliary_loss_weight * kl_aux_loss / ptn).mean()), dtype=torch.float64)
+        return out

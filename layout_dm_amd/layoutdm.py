@@ -212,7 +212,8 @@ class LayoutDM:
         inner = HipMaskAndReplaceDiffusion(
             n_category=tokenizer.N_category, n_bin=tokenizer.N_bbox_per_var, max_elem=tokenizer.max_seq_length,
             n_attr=tokenizer.N_var_per_element, d_model=d_model, n_head=n_head, d_ff=d_ff, n_layer=n_layer,
-            num_timesteps=num_timesteps, precision=precision, max_batch=max_batch, device=device, q_type=q_type)
+            num_timesteps=num_timesteps, precision=precision, max_batch=max_batch, device=device, q_type=q_type,
+            auxiliary_loss_weight=auxiliary_loss_weight)
         assert inner.num_classes == tokenizer.N_total and inner.max_token_length == tokenizer.max_token_length
         self.model = _ModuleShim(inner, self)
         self._refine_table = None
@@ -242,6 +243,39 @@ class LayoutDM:
         raise NotImplementedError("training forward is out of scope (SURVEY §2.1 #10)")
 
     __call__ = forward
+
+    # ---- held-out layouts: the variational bound and main.evaluate's loss (no gradients) --------------------------------
+    def _seq_of(self, seq_or_layouts) -> torch.Tensor:
+        if isinstance(seq_or_layouts, dict):
+            if "seq" in seq_or_layouts:
+                return torch.as_tensor(seq_or_layouts["seq"])
+            return self.encode(seq_or_layouts)["seq"]     # raw {"bbox", "label", "mask"}: tokenizer.encode on the GPU
+        return torch.as_tensor(seq_or_layouts)
+
+    def score(self, seq_or_layouts, n_draws: int = 1, seed: Optional[int] = None, first_layout: int = 0) -> torch.Tensor:
+        """Per-layout variational bound on -log p(layout) in nats per token, (B,) float64 on the device
+        (HipMaskAndReplaceDiffusion.elbo: sum over t of the reference's kl_loss term at one drawn x_t per t; no prior term
+        L_T, like the reference's bound).  seq_or_layouts: (B,S) ids, {"seq": ids} or raw {"bbox", "label", "mask"}.
+        Lower is better explained; the same seed makes two checkpoints (or two candidate layouts) comparable."""
+        return self.model.module.elbo(self._seq_of(seq_or_layouts), n_draws=n_draws, seed=seed, first_layout=first_layout)
+
+    def evaluate_loss(self, seq_or_layouts, batch_size: int = 64, seed: Optional[int] = None) -> float:
+        """main.evaluate (trainer/main.py:271-294) on held-out layouts: the mean over batches of kl_loss + aux_loss — the
+        number that picks best_model.pt and is written to result.json as test_loss.  It INCLUDES the auxiliary term:
+        LayoutDM.forward calls the diffusion with is_train=True even under evaluate().  One t per layout per batch
+        (sample_time on torch's global CPU generator, like the reference), x_t from the Philox stream keyed by
+        (seed, index of the layout in `seq`, t, position).  forward() itself stays unavailable: there is no gradient."""
+        seq = self._seq_of(seq_or_layouts)
+        inner = self.model.module
+        seed = inner._draw_seed(seed)
+        total, steps = 0.0, 0
+        for off in range(0, seq.shape[0], int(batch_size)):
+            losses = inner.loss(seq[off:off + int(batch_size)], seed=seed, first_layout=off)
+            total += float(sum(v.item() for v in losses.values()))
+            steps += 1
+        if steps == 0:
+            raise ValueError("evaluate_loss: no layouts")
+        return total / steps
 
     # ---- base_model.py:124-150 + layoutdm.py:90-97 -------------------------------------------------
     def aggregate_sampling_settings(self, sampling_cfg, args):
