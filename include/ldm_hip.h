@@ -213,6 +213,10 @@ int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, 
 int ldm_set_tie_report(ldm_handle* h, float tie_rel, float tie_abs);
 /* flags of the most recent deterministic call: d_flags (n_steps, B) uint8, row i = i-th step of that call */
 int ldm_get_tie_flags(ldm_handle* h, uint8_t* d_flags, int n_steps, int B, void* stream);
+/* Development hook: which layouts of the most recent ldm_sample_loop call read their first step's logits from the handle's
+ * step-0 table instead of running the denoiser (one-launch loop, all-[MASK] layouts: ldm_describe `step0_cache`).  host_out
+ * (n) uint8 on the HOST, n <= max_batch; synchronises the device.  Fails where the handle has no such loop. */
+int ldm_dev_step0_flags(ldm_handle* h, uint8_t* host_out, int n);
 
 /* ---- cond=relation, split-step form ------------------------------------------------------- */
 /* The logit adjustment alone (`num_update` SGD steps on the mean relational-constraint loss, analytic gradient;

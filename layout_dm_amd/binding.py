@@ -27,7 +27,7 @@ EXPORTS = (
     "ldm_denoise_logits", "ldm_posterior", "ldm_sample_tokens", "ldm_sample_step", "ldm_sample_loop",
     "ldm_decode_layouts", "ldm_relation_update", "ldm_set_tie_report", "ldm_get_tie_flags",
     "ldm_last_loop_ms", "ldm_set_profiling", "ldm_profile_count", "ldm_profile_get", "ldm_profile_reset",
-    "ldm_abi_version", "ldm_get_layout", "ldm_describe",
+    "ldm_abi_version", "ldm_get_layout", "ldm_describe", "ldm_dev_step0_flags",
     # FID feature extractor (bound in layout_dm_amd/fid.py)
     "ldm_fid_create", "ldm_fid_destroy", "ldm_fid_last_error", "ldm_fid_load_weight", "ldm_fid_finalize",
     "ldm_fid_features", "ldm_prdc", "ldm_layout_metrics",
@@ -130,6 +130,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_relation_update.argtypes = [vp, vp, vp, C.POINTER(LdmRelation), i32, i32, vp]
     lib.ldm_set_tie_report.argtypes = [vp, C.c_float, C.c_float]
     lib.ldm_get_tie_flags.argtypes = [vp, vp, i32, i32, vp]
+    lib.ldm_dev_step0_flags.argtypes = [vp, vp, i32]
     lib.ldm_last_loop_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ldm_set_profiling.argtypes = [vp, i32]
     lib.ldm_profile_count.argtypes = [vp]
@@ -465,6 +466,13 @@ class Engine:
                     "ldm_get_tie_flags")
         return out
 
+    def step0_flags(self, B: int) -> np.ndarray:
+        """Development hook: (B,) uint8, 1 where a layout of the most recent sample_loop call read its first step's logits
+        from the handle's step-0 table (an all-[MASK] start on the one-launch loop) instead of running the denoiser."""
+        out = np.zeros(int(B), dtype=np.uint8)
+        self._check(self.lib.ldm_dev_step0_flags(self._h, out.ctypes.data_as(C.c_void_p), int(B)), "ldm_dev_step0_flags")
+        return out
+
     # ------------------------------------------------------------------ cond=relation
     def make_relation(self, graph, centres, canvas_bins, relation_lambda: float, num_update: int, n_graph_total: int):
         """Device-side description of cond["batch_w_canvas"] for ldm_relation_update.  graph: object / dict with
@@ -542,6 +550,9 @@ class Engine:
                 out[k] = buf.value.decode().split("knobs=", 1)[1]
                 break
             out[k] = v
+        # the step-0 logits cache of the one-launch loop: on / off and its (first timestep, S) keys, oldest first
+        out["step0_cache"] = {"enabled": out.pop("step0_cache", "off") == "on",
+                              "entries": [[int(x) for x in e.split(":")] for e in out.pop("step0_entries", "").split(",") if e]}
         return out
 
     def last_loop_ms(self) -> float:

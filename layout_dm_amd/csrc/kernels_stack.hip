@@ -19,7 +19,9 @@
 // constrained posterior, cond overrides, draw: ldm_post_token.h on 16-lane groups, four tokens per wavefront) on the
 // layout's logits in LDS.  One launch per sampling call; per step nothing touches memory but the weight stream (L2 /
 // Infinity Cache resident), the 125 cond tokens and, on request, the intermediate tokens.  No hipGraph, no chunk
-// pipelines, no logits / row / embedding round trips.
+// pipelines, no logits / row / embedding round trips.  A layout that starts all-[MASK] (every layout of an unconditional
+// call) skips the denoiser pass of its first step: those logits depend on the checkpoint, the timestep and S alone and
+// come from a table the same kernel wrote once (StackArgs logits0 / logits0_out).
 //
 // Between layers nothing touches memory but the weight stream.  Weight image per layer: ldm_pack::pack_attn_head_image
 // (per head 6 in_proj tiles + its 2 out-proj slabs, 9-slot ring cycle: see SlabPair) and the k-slot FFN image.
@@ -55,6 +57,12 @@ struct StackArgs {
   // REL: cond=relation (base.py:261-269) — the graph of the launch's layouts (edge_off + workgroup index) and its n_bin
   RelGraph rel;
   int rel_n_bin;
+  // HEAD == 2, step-0 shortcut: the first step's logits of an all-[MASK] layout are a constant of the checkpoint, t_model[0]
+  // and S.  logits0 = that constant as the five head tiles in register order [(ht * 16 + i) * 256 + thread] (or nullptr);
+  // logits0_out != nullptr: this launch (one layout) writes it; step0_flags[layout] = 1 where the shortcut was taken
+  const float* logits0;
+  float* logits0_out;
+  uint8_t* step0_flags;
 };
 // HEAD == 2 reads its loop parameters from the kernel-argument segment AT THE POINT OF USE, through a pointer hipcc
 // cannot see through: hoisted out of the step loop they would occupy ~60 SGPRs for the whole kernel, which already
@@ -70,8 +78,10 @@ constexpr int kPostRows = 128 * kPostLd * 4;  // bytes of the logits rows; behin
 constexpr int kStackLoopB1 = 2048;            // HEAD == 2: the linear1 bias table is padded to whole 1-KiB DMA pieces
 constexpr int kStackLoopRelLds = REL_MAX_EDGE * 4 + 4 * 32 * 4 + 16;  // REL: the layout's edges, packed | cluster centres [4][32] | edge count —
                                                                      // staged once per launch (RelPersist), behind kStackLoopLds
-constexpr int kStackLoopLds = 1024 + 128 + 2304;  // HEAD == 2: tokens [128] | cond token + strong bit [128] | REL: element -> graph
-                                                  // node [32] | incidence lists of the graph's nodes (ldm_relation_core.h kRelIncBytes)
+constexpr int kStackLoopLds = 1024 + 128 + 2304 + 16;  // HEAD == 2: tokens [128] | cond token + strong bit [128] | REL: element -> graph
+                                                       // node [32] | incidence lists of the graph's nodes (ldm_relation_core.h kRelIncBytes)
+                                                       // | step-0 shortcut: one "miss" word per wavefront
+constexpr int kStackLoopStep0Word = (1024 + 128 + 2304) / 4;  // ... as an index into the tokens' ints
 static_assert(kRelIncBytes <= 2304, "incidence lists outgrow their LDS slot");
 static_assert(kRelScratchFloats * 4 <= 2 * KV_BYTES, "the SGD's scratch lives in the K / V buffers");
 
@@ -116,13 +126,23 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
     const stack_kargs_ptr kp = stack_kargs();
     const int S = kp->S;
     int* toks = reinterpret_cast<int*>(smem + 3 * STAGE + 2 * KV_BYTES + (3 * kp->H * 64 + 2 * LN_DP + 512 + kStackLoopB1 + 2 * LN_DP + 512) * 4);
+    bool not_mask = false;
     if (tid_o < 128) {
       const int s = tid_o < S ? tid_o : S - 1;
       const size_t row = (size_t)b_o * S + s;
-      toks[tid_o] = kp->post.tokens[row];
+      const int tk = kp->post.tokens[row];
+      toks[tid_o] = tk;
+      not_mask = tk != kp->post.v.mask_id;
       int cc = -1;
       if (kp->post.cond_seq) cc = kp->post.cond_seq[row] | ((kp->post.strong && kp->post.strong[row]) ? (1 << 30) : 0);
       toks[128 + tid_o] = cc;
+    }
+    // step-0 shortcut: a cached table exists and every token of the layout is [MASK] — nothing else enters (cond overrides,
+    // weak logits, [PAD] disable and the sampler act in the tail, which runs either way).  One word per wavefront, != 0 = miss;
+    // step 0 reads the four back (no register is carried into the step loop)
+    {
+      const bool miss = __any(not_mask) != 0 || kp->logits0 == nullptr;
+      if ((tid_o & 63) == 0) toks[kStackLoopStep0Word + wave_o] = miss ? 1 : 0;
     }
     if constexpr (REL) {  // element -> node of the layout's relation graph (node 0 = canvas), -1 = [PAD] element
       if (tid_o == 0) {
@@ -240,6 +260,17 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
     for (int k = 0; k < 4; ++k) dma_lin4(voff, img + wave * 8192 + (k >> 1) * STAGE + (k & 1) * 4096,
                                          lds0 + wave * 8192 + (k >> 1) * STAGE + (k & 1) * 4096);
   };
+  // step-0 shortcut (HEAD == 2): the logits of this step are known — a uniform branch around the whole denoiser pass, from
+  // the step prologue to the end of the vocabulary head.  Every barrier and every DMA of the pass starts behind this
+  // point, so the skipping side leaves nothing in flight and all four wavefronts take the same side.
+  bool skip0 = false;
+  if constexpr (HEAD == 2) {
+    if (it == 0) {
+      const int4 m = *reinterpret_cast<const int4*>(toks + kStackLoopStep0Word);
+      skip0 = __builtin_amdgcn_readfirstlane((m.x | m.y | m.z | m.w) == 0 ? 1 : 0) != 0;
+    }
+  }
+  if (!skip0) {  // (not indented: the denoiser pass)
   int t_model = 0;
   if constexpr (HEAD == 2) t_model = stack_kargs()->t_model[it];
   static_assert(NGV == 4 * NT2 - 2, "columns 464..479 (the last two groups of tile NT2 - 1) are padding: zero, written with the gather");
@@ -642,8 +673,10 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         F.template step<0, true, 1>();
       }
       if (c <= A.n_chunks) {
+        // the odd last iteration issues no DMA: its "next chunk" would be chunk 0 again, 64 KiB per layer into a ring
+        // stage nobody reads any more (the next phase refills the ring behind a barrier of its own)
         chunk_args(c);
-        F.template step<0, true, 0>();
+        F.template step<0, false, 0>();
       }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -732,10 +765,10 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) relW[k] = lds0 + r3 * RKB + ((((k << 1) | hi3) ^ (r3 & 15)) << 4);
     if constexpr (HEAD == 2) {
-      // ---- the step's tail in the same workgroup.  The five 32-class tiles stay in the (dead) residual accumulators;
-      // when the last one is done the weight ring is free and takes the layout's logits as [token][kPostLd] floats.
+      // The five 32-class tiles stay in the (dead) residual accumulators for the step's tail below; when the last one is
+      // done the weight ring is free and takes the layout's logits as [token][kPostLd] floats.
       constexpr int NHT = 5;  // launcher: n_head_tiles == 5
-      constexpr int NA = 5;   // launcher: n_attr == 5 (c x y w h)
+      static_assert(NHT * 16 * 256 == kStackStep0Floats, "the step-0 table holds the head tiles of one layout in register order");
 #pragma unroll
       for (int ht = 0; ht < NHT; ++ht) {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -753,6 +786,58 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
         asm volatile("" : "+a"(lg));
         acc[ht] = lg;
       }
+      if (float* l0 = stack_kargs()->logits0_out) {  // the launch that builds the step-0 table (one layout): tiles in register order
+        l0 += tid_now();
+#pragma unroll
+        for (int ht = 0; ht < NHT; ++ht) {
+          const f32x16 tile = acc[ht];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) l0[(ht * 16 + i) * 256] = tile[i];
+        }
+      }
+    } else
+    for (int ht = 0; ht < A.n_head_tiles; ++ht) {
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // tile ht (and every earlier piece) has landed
+      __builtin_amdgcn_s_barrier();                                // ... everybody's; tile ht - 1 is read by nobody any more
+      asm volatile("" ::: "memory");
+      if (ht + 3 < A.n_head_tiles) dma_head_tile(ht + 3);          // -> stage of tile ht - 1
+      TilePipe<KS, 8> TP;
+      TP.xf = xf3;
+      TP.voff = voff;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) TP.aW[k] = relW[k] + (unsigned)(ht & 3) * STAGE;
+      TP.template run<false, false>();
+      // D[i = class][j = row]: lane (row, hi) holds classes 32 ht + 8 rq + 4 hi + i
+      f32x16 lg = TP.acc;
+      asm volatile("s_nop 7\n\ts_nop 7" : "+v"(lg));
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq)
+        if (valid3)
+          *reinterpret_cast<float4*>(lrow + ht * 32 + rq * 8) = make_float4(lg[rq * 4 + 0], lg[rq * 4 + 1], lg[rq * 4 + 2], lg[rq * 4 + 3]);
+    }
+  }
+  } else if constexpr (HEAD == 2) {
+    // the same five tiles from the table, into the same registers
+    const stack_kargs_ptr kp = stack_kargs();
+    const float* l0 = kp->logits0 + tid_now();
+#pragma unroll
+    for (int ht = 0; ht < kStackStep0Floats / (16 * 256); ++ht) {
+      f32x16 tile;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tile[i] = l0[(ht * 16 + i) * 256];
+      asm volatile("" : "+a"(tile));
+      acc[ht] = tile;
+    }
+    if (kp->step0_flags && tid_now() == 0) kp->step0_flags[b] = 1;
+  }
+  if constexpr (HEAD == 2) {
+    {
+      // ---- the step's tail in the same workgroup, on the five tiles in acc[0 .. NHT) (computed above, or read from the table)
+      constexpr int NHT = 5;  // launcher: n_head_tiles == 5
+      constexpr int NA = 5;   // launcher: n_attr == 5 (c x y w h)
+      const int lane3 = stack_lane_id();
+      const int hi3 = lane3 >> 5;
+      const int row3 = wave * 32 + (lane3 & 31);
       __builtin_amdgcn_s_barrier();  // nobody reads the ring any more
       asm volatile("" ::: "memory");
       const stack_kargs_ptr kp = stack_kargs();
@@ -977,25 +1062,6 @@ __global__ __launch_bounds__(256, 1) void stack_stream_k(StackArgs a) {
           }
         }
       }
-    } else
-    for (int ht = 0; ht < A.n_head_tiles; ++ht) {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // tile ht (and every earlier piece) has landed
-      __builtin_amdgcn_s_barrier();                                // ... everybody's; tile ht - 1 is read by nobody any more
-      asm volatile("" ::: "memory");
-      if (ht + 3 < A.n_head_tiles) dma_head_tile(ht + 3);          // -> stage of tile ht - 1
-      TilePipe<KS, 8> TP;
-      TP.xf = xf3;
-      TP.voff = voff;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) TP.aW[k] = relW[k] + (unsigned)(ht & 3) * STAGE;
-      TP.template run<false, false>();
-      // D[i = class][j = row]: lane (row, hi) holds classes 32 ht + 8 rq + 4 hi + i
-      f32x16 lg = TP.acc;
-      asm volatile("s_nop 7\n\ts_nop 7" : "+v"(lg));
-#pragma unroll
-      for (int rq = 0; rq < 4; ++rq)
-        if (valid3)
-          *reinterpret_cast<float4*>(lrow + ht * 32 + rq * 8) = make_float4(lg[rq * 4 + 0], lg[rq * 4 + 1], lg[rq * 4 + 2], lg[rq * 4 + 3]);
     }
   }
   } while (HEAD == 2 && ++it < n_iter);  // step loop
@@ -1058,6 +1124,7 @@ void launch_stack_loop(const FusedLayerSet& ls, int F, int N, int B, int S, int 
   a.head_img = (const char*)head.img; a.head_g = head.g; a.head_b = head.b; a.n_head_tiles = head.n_tiles;
   a.post = *lp.post; a.adaln = lp.adaln; a.tbl = lp.tables; a.inter = lp.inter;
   a.n_steps = lp.n_steps; a.inter_ld = lp.inter_ld; a.tie_ld = lp.tie_ld;
+  a.logits0 = lp.logits0; a.logits0_out = B == 1 ? lp.logits0_out : nullptr; a.step0_flags = lp.step0_flags;
   for (int i = 0; i < lp.n_steps && i < kStackLoopMaxSteps; ++i) {
     a.t_model[i] = (int16_t)lp.t_model[i];
     a.t_post[i] = (int16_t)lp.t_post[i];

@@ -137,6 +137,7 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
     if (const char* fa = knob_env("LDM_FUSED_ATTN")) h->fused_attn = atoi(fa) == 0 ? 0 : 6;
     if (const char* sp = knob_env("LDM_STACK_LOOP")) h->stack_loop = atoi(sp);
     h->rel_loop = knob_int("LDM_REL_LOOP", 1);
+    h->step0_cache = knob_int("LDM_STEP0_CACHE", 1) != 0 ? 1 : 0;
     // stack kernel: one 128-row tile per layout, and every one of its 4 waves must own at least one real row (its
     // exec-masked stores are counted by the vmcnt waits) => 96 < S <= 128; d_model 464 in 8 heads, K padded to 512
     if (h->S > 128 || h->S <= 96 || h->dh > 64 || h->D != 464 || h->Dq != 512 || h->HD != 512 || h->H != 8 ||
@@ -232,10 +233,23 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
   A(&h->st_strong, (size_t)cfg->max_batch * h->S);
   A(&h->rng, 2);
   A(&h->sched, (size_t)kNumSched * cfg->n_attr * (h->T + 1));
+  if (cfg->precision == LDM_PREC_FAST_F16 && h->fused_attn == 6) {  // step-0 logits cache of the one-launch loop (ldm_handle.h)
+    A(&h->step0_tab, (size_t)ldm_handle::kStep0Slots * kStackStep0Floats);
+    A(&h->step0_tok, (size_t)2 * h->S);
+    A(&h->step0_flags, (size_t)cfg->max_batch);
+  }
   if (rc != 0) {
     create_error() = h->err;
     ldm_destroy(h);
     return rc;
+  }
+  if (h->step0_tok) {
+    const std::vector<int32_t> row((size_t)h->S, h->vocab.mask_id);
+    if (hipMemcpy(h->step0_tok, row.data(), row.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      create_error() = "hipMemcpy of the all-[MASK] row failed";
+      ldm_destroy(h);
+      return -2;
+    }
   }
   if (hipEventCreate(&h->loop_a) != hipSuccess || hipEventCreate(&h->loop_b) != hipSuccess ||
       hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming) != hipSuccess) {
@@ -270,6 +284,8 @@ extern "C" void ldm_destroy(ldm_handle* h) {
   if (h->loop_a) (void)hipEventDestroy(h->loop_a);
   if (h->loop_b) (void)hipEventDestroy(h->loop_b);
   if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
+  for (auto ev : h->step0_ev)
+    if (ev) (void)hipEventDestroy(ev);
   for (auto st : h->lane_stream)
     if (st) (void)hipStreamDestroy(st);
   for (auto ev : h->lane_done)
@@ -452,6 +468,10 @@ extern "C" int ldm_describe(const ldm_handle* h, char* buf, int cap) {
   s += ";round=" + std::to_string(loop ? h->n_cu : h->chunk * std::max(h->n_lanes, 1));
   s += std::string(";batch_rule=") + (loop ? "whole_rounds_of_one_workgroup_per_layout" : "whole_chunks");
   s += std::string(";src_digest=") + (ldm_build_source_digest + sizeof("LDM_SRC_DIGEST=") - 1);
+  // step-0 logits cache of the one-launch loop: on / off, and the (first timestep : S) keys it holds, oldest first
+  s += std::string(";step0_cache=") + (loop && h->step0_cache && h->step0_tab ? "on" : "off") + ";step0_entries=";
+  for (size_t i = 0; i < h->step0.size(); ++i)
+    s += (i ? "," : "") + std::to_string(h->step0[i].t) + ":" + std::to_string(h->step0[i].S);
   s += ";knobs=" + knobs_honoured();
   if (buf && cap > 0) {
     const size_t n = std::min((size_t)cap - 1, s.size());

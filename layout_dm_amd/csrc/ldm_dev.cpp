@@ -41,6 +41,18 @@ extern "C" void ldm_dev_stack_phases(unsigned long long* out16) { ldm::stack_pha
 extern "C" void ldm_dev_lngemm_phases(unsigned long long* out8) { ldm::lngemm_phase_read(out8); }
 extern "C" void ldm_dev_attnout_phases(unsigned long long* out24) { ldm::attnout_phase_read(out24); }
 
+// Which layouts of the most recent ldm_sample_loop call took the step-0 shortcut of the one-launch loop (their first step's logits
+// read from the handle's table): the proof that the path ran (tests/test_step0_cache_gpu.py).  host_out: n bytes on the host.
+extern "C" int ldm_dev_step0_flags(ldm_handle* h, uint8_t* host_out, int n) {
+  if (!h || !host_out) return -1;
+  if (!h->step0_flags) return h->fail(-1, "the handle has no one-launch loop (no step-0 flags)");
+  if (n < 1 || n > h->cfg.max_batch) return h->fail(-1, "n outside [1, max_batch]");
+  ON_DEVICE(h);
+  HIP_OK(h, hipDeviceSynchronize());
+  HIP_OK(h, hipMemcpy(host_out, h->step0_flags, (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Unit check of the split mode's fused attention + out_proj launch (kernels_attnout.hip) on synthetic operands against a float64
 // host computation of the same block: q / k / v (amplitude qk_amp / 1) -> hi / lo panels as in_proj's epilogue writes them, out_proj
 // weights with max |w| in [1, 2) (what ldm_weights.cpp make_w16's power-of-two pre-scale produces) -> k-step image, residual rows,

@@ -218,6 +218,23 @@ struct ldm_handle {
   int stack_loop = 1;  // the WHOLE reverse loop of a layout in its workgroup (kernels_stack.hip HEAD == 2): one launch per
                        // sampling call, the step's tail behind the vocabulary head (LDM_STACK_LOOP=0: one stack launch +
                        // one posterior launch per step, captured in per-lane hipGraphs — the r02 path)
+  // Step-0 logits cache of the one-launch loop (ldm_loop.cpp run_loop_fused, kernels_stack.hip): an unconditional call starts
+  // from all-[MASK] layouts, whose first denoiser pass depends on the checkpoint, the first timestep and S alone.  The first
+  // ldm_sample_loop call with a new (t_model[0], S) runs that pass once for ONE layout (same kernel, writing the head's tiles
+  // in register order) on the caller's stream in front of the real launch; from then on every all-[MASK] layout reads the table.
+  // At most kStep0Slots keys, the oldest replaced; every (re)load of a weight drops all of them (LDM_DEV=1 LDM_STEP0_CACHE=0: off).
+  struct Step0Entry {
+    int t = -1, S = 0, slot = 0;
+    hipStream_t built_on = nullptr;   // the build is ordered in front of later work of this stream ...
+    bool settled = false;             // ... and, once its event has been seen complete, of every stream
+  };
+  static constexpr int kStep0Slots = 4;
+  int step0_cache = 1;
+  float* step0_tab = nullptr;        // [kStep0Slots][kStackStep0Floats]
+  int32_t* step0_tok = nullptr;      // an all-[MASK] row [S] | the build launch's token output [S]
+  uint8_t* step0_flags = nullptr;    // [max_batch]: 1 = the layout of the last ldm_sample_loop call took the shortcut
+  hipEvent_t step0_ev[kStep0Slots] = {nullptr, nullptr, nullptr, nullptr};
+  std::vector<Step0Entry> step0;     // oldest first
   // near-tie report of deterministic decoding (ldm_set_tie_report): flags [tie_steps][max_batch]
   float tie_rel = 0.f, tie_abs = 0.f;
   uint8_t* tie_flags = nullptr;

@@ -174,7 +174,16 @@ struct StackLoop {
   int n_steps, inter_ld;
   int tie_ld;                // post->tie_flags of step i at + i * tie_ld (per layout of this launch)
   const struct RelArgs* rel; // cond=relation: the graph of the launch's layouts (edge_off advanced to its first layout), or nullptr
+  // step-0 shortcut: the first step's logits of an all-[MASK] layout depend on the checkpoint, t_model[0] and S alone.
+  // logits0 (or nullptr): that table, kStackStep0Floats floats as the kernel's five head tiles in register order
+  // [(tile * 16 + i) * 256 + thread]; a workgroup whose layout starts all-[MASK] reads its first step's logits from it
+  // instead of running the denoiser pass, and sets step0_flags[layout of the launch] (or nullptr).
+  // logits0_out (or nullptr): a launch of ONE layout writes the table behind its vocabulary head.
+  const float* logits0;
+  float* logits0_out;
+  uint8_t* step0_flags;
 };
+constexpr int kStackStep0Floats = 5 * 16 * 256;
 // largest sub-vocabulary (body + [PAD] + [MASK]) the fused tail takes: 3 class slots on each of a group's 16 lanes
 constexpr int kStackPostMaxLive = 48;
 constexpr int kStackLoopMaxSteps = 128;  // timesteps travel in the kernel arguments

@@ -33,6 +33,7 @@ inline const std::map<std::string, const char*>& knob_table() {
       {"LDM_LNGEMM_TM", "row-resident LayerNorm + x3 GEMM: phase-timer instantiation (tools/lngemm_probe.py)"},
       {"LDM_LNGEMM_ABL", "row-resident LayerNorm + x3 GEMM: compile-time timing variants, measurement build only (tools/build_measurement_variants.py lngemm; WRONG NUMERICS)"},
       {"LDM_REL_LOOP", "0 = cond=relation on the per-step path instead of inside the one-launch loop (fast mode)"},
+      {"LDM_STEP0_CACHE", "0 = every layout of the one-launch loop runs the denoiser pass of its first step, instead of all-[MASK] layouts reading that step's logits from the handle's table"},
   };
   return t;
 }

@@ -207,12 +207,71 @@ bool ldm_host::loop_fusable(const ldm_handle* h, const ldm_relation* rel) {
          h->T < 32768 && !h->fast.empty() && h->tbl_att_dyn && h->D == 464 && h->F <= 2048;
 }
 
+// The step-0 logits table of (t0, S) for a launch on `st` (ldm_handle.h Step0Entry), built on first use; *tab = nullptr
+// where this call has to run without it: the cache is off, the stream is being captured and the table is not known to be
+// complete (the build must not be recorded into the caller's graph), or another stream's build is still in flight.
+static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& hd, int t0, int t_post0, hipStream_t st,
+                       const float** tab) {
+  *tab = nullptr;
+  if (!h->step0_cache || !h->step0_tab) return 0;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  bool capturing = false;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess) {  // (e.g. the null stream while another stream captures globally)
+    (void)hipGetLastError();
+    capturing = true;
+  } else {
+    capturing = cs != hipStreamCaptureStatusNone;
+  }
+  for (auto& e : h->step0) {
+    if (e.t != t0 || e.S != h->S) continue;
+    if (!e.settled && !capturing && hipEventQuery(h->step0_ev[e.slot]) == hipSuccess) e.settled = true;
+    (void)hipGetLastError();  // (hipErrorNotReady is not an error of this call)
+    if (e.settled || (!capturing && e.built_on == st)) *tab = h->step0_tab + (size_t)e.slot * kStackStep0Floats;
+    return 0;
+  }
+  if (capturing) return 0;
+  ldm_handle::Step0Entry e;
+  e.t = t0; e.S = h->S; e.built_on = st;
+  if ((int)h->step0.size() >= ldm_handle::kStep0Slots) {  // replace the oldest, once no launch of any stream can still read it
+    e.slot = h->step0.front().slot;
+    h->step0.erase(h->step0.begin());
+    HIP_OK(h, hipDeviceSynchronize());
+  } else {
+    e.slot = (int)h->step0.size();
+  }
+  if (!h->step0_ev[e.slot]) HIP_OK(h, hipEventCreateWithFlags(&h->step0_ev[e.slot], hipEventDisableTiming));
+  // the SAME instantiation as the real launch, one all-[MASK] layout, one step: the table holds what that kernel's registers held
+  ldm_sampler det{};
+  det.kind = LDM_SAMPLE_DETERMINISTIC;
+  det.temperature = 1.f;
+  PostArgs p{};
+  fill_post(h, p, nullptr, &det, 0, 1);
+  p.tokens = h->step0_tok;
+  p.tokens_out = h->step0_tok + h->S;
+  p.emb = h->emb; p.pos = h->pos; p.D = h->D;
+  const int32_t tm = t0, tp = t_post0;
+  StackLoop lp{};
+  lp.tables = StackTables{h->tbl_att_static, h->tbl_att_dyn, h->tbl_ffn, h->tbl_head};
+  lp.post = &p; lp.adaln = h->adaln; lp.t_model = &tm; lp.t_post = &tp;
+  lp.n_steps = 1; lp.inter_ld = 1; lp.tie_ld = h->cfg.max_batch;
+  lp.logits0_out = h->step0_tab + (size_t)e.slot * kStackStep0Floats;
+  {
+    ldm_handle::Scope sc(h, st, "step0_logits_build", 0, (double)kStackStep0Floats * 4);
+    launch_stack_loop(ls, h->F, h->D, 1, h->S, h->H, h->dh, hd, lp, st);
+  }
+  HIP_OK(h, hipEventRecord(h->step0_ev[e.slot], st));
+  h->step0.push_back(e);
+  *tab = lp.logits0_out;
+  return 0;
+}
+
 // tokens_in -> tokens_out (may alias) through n_steps reverse steps; step0 = loop index of the first one (RNG counter
 // word); cond pointers describe layout 0..B of this call; d_inter (n_steps, B, S) or nullptr; tie_row0 >= 0: near-tie
-// flags of step i go to row tie_row0 + i of h->tie_flags
+// flags of step i go to row tie_row0 + i of h->tie_flags; from_start: tokens_in is the start of a sampling call
+// (ldm_sample_loop), whose all-[MASK] layouts may read their first step's logits from the handle's table
 static int run_loop_fused(ldm_handle* h, const int32_t* tin, int32_t* tout, const ldm_cond* cond, const ldm_relation* rel,
                           const int32_t* t_model, const int32_t* t_post, int n_steps, const ldm_sampler* s, int step0, int B,
-                          int32_t* d_inter, int tie_row0, hipStream_t st) {
+                          int32_t* d_inter, int tie_row0, hipStream_t st, bool from_start = false) {
   const int D = h->D, F = h->F, M = B * h->S;
   FusedLayerSet ls{};
   ls.n_layer = h->L;
@@ -222,8 +281,15 @@ static int run_loop_fused(ldm_handle* h, const int32_t* tin, int32_t* tout, cons
                           h->fast[i].ffn_img_pipe, w.b1, w.b2, w.g2, w.be2};
   }
   const StackHead hd{h->head_img_ks, h->head_g, h->head_b, nullptr, h->Cp, h->Cp / 32};
+  // (the roofline stays against the algorithmic work: n * step_flops, although the first pass of an all-[MASK] layout is a table read)
   const double step_flops = h->L * (gemm_flops(M, 3 * D, D) + 4.0 * B * h->H * (double)h->S * h->S * h->dh +
                                     gemm_flops(M, D, D) + 2 * gemm_flops(M, F, D)) + gemm_flops(M, h->C, D);
+  const float* logits0 = nullptr;
+  if (from_start && h->step0_flags) {
+    int rc = step0_table(h, ls, hd, t_model[0], t_post[0], st, &logits0);
+    if (rc) return rc;
+    HIP_OK(h, hipMemsetAsync(h->step0_flags, 0, (size_t)B, st));
+  }
   for (int i0 = 0; i0 < n_steps; i0 += kStackLoopMaxSteps) {  // (timesteps travel in the kernel arguments)
     const int n = std::min(kStackLoopMaxSteps, n_steps - i0);
     PostArgs p{};
@@ -249,6 +315,9 @@ static int run_loop_fused(ldm_handle* h, const int32_t* tin, int32_t* tout, cons
     lp.inter = d_inter ? d_inter + (size_t)i0 * B * h->S : nullptr;
     lp.n_steps = n; lp.inter_ld = B; lp.tie_ld = h->cfg.max_batch;
     lp.rel = rel ? &ra : nullptr;
+    // (only the first segment of a call can start all-[MASK]; the kernel tests the tokens itself either way)
+    lp.logits0 = i0 == 0 ? logits0 : nullptr;
+    lp.step0_flags = i0 == 0 && from_start ? h->step0_flags : nullptr;
     ldm_handle::Scope sc(h, st, "layers_fused_loop", n * step_flops, (double)B * h->S * 8);
     launch_stack_loop(ls, F, D, B, h->S, h->H, h->dh, hd, lp, st);
   }
@@ -363,7 +432,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
   if (loop_fusable(h, rel)) {
     // one launch: every layout's workgroup runs all its steps in place on the caller's tokens (no staging, no graph)
     if ((rc = run_loop_fused(h, d_tokens_inout, d_tokens_inout, cond, rel, h_t_model, h_t_post, n_steps, s, 0, B,
-                             d_intermediates, 0, st)))
+                             d_intermediates, 0, st, true)))
       return rc;
     HIP_OK(h, hipEventRecord(h->loop_b, st));
     h->loop_timed = true;

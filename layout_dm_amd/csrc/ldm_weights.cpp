@@ -37,6 +37,7 @@ extern "C" int ldm_load_weight(ldm_handle* h, const char* key, const float* h_da
   HIP_OK(h, hipMemcpy(r.d, h_data, n * sizeof(float), hipMemcpyHostToDevice));
   h->raw[k] = r;
   h->finalized = false;
+  h->step0.clear();  // (the step-0 logits tables are a function of the checkpoint)
   return 0;
 }
 
@@ -353,6 +354,7 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
   h->finalized = false;   // (a finalize that fails part-way must not leave an earlier success standing over freed images)
   for (auto& g : h->graphs) g.destroy();
   h->graphs.clear();
+  h->step0.clear();  // the step-0 logits tables of the loop kernel belong to the weights that are being replaced
   for (void* p : h->derived) (void)hipFree(p);
   h->derived.clear();
   h->fast.clear();
