@@ -122,7 +122,9 @@ typedef struct {
 /* ---- lifecycle ----------------------------------------------------------------------
  * ldm_create validates the whole geometry BEFORE it touches a device and returns -1 with ldm_last_error(NULL) naming
  * the field: n_attr == 5; d_model, d_ff multiples of 16, d_model <= 1024; d_model % n_head == 0, head dimension <= 64;
- * n_category + 4 n_bin + 2 <= 192 classes; max_elem * n_attr <= 128 tokens in LDM_PREC_FAST_F16 (one score tile per
+ * n_bin <= 128 and n_category + 4 n_bin + 2 <= 576 classes in LDM_PREC_EXACT_F32 / LDM_PREC_SPLIT_F16, <= 192 classes in
+ * the fp16 modes (fast / mixed / hybrid: the message names the precision and points to split / exact; cond=relation
+ * stays at n_bin <= 32 in every mode, rc -4); max_elem * n_attr <= 128 tokens in LDM_PREC_FAST_F16 (one score tile per
  * head; longer sequences: LDM_PREC_EXACT_F32, bounded by the LDS: 2 * S * head_dim floats <= 160 KiB).  The reference's
  * own configurations (rico25 / publaynet on the 464 / 8 / 1856 backbone, S = 125) run on the layout-resident kernels,
  * every other accepted geometry on generic tiled kernels (same numerics contract, lower throughput). */

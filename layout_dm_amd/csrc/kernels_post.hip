@@ -1,5 +1,5 @@
 // Fused tail of one reverse step, one 64-lane wavefront per token (lane l owns classes l, l+64,
-// l+128 of the <=192-class vocabulary), everything in registers + wave shuffles:
+// l+128 of the <=192-class vocabulary; l + 64 j, j < 9, of a wide one), everything in registers + wave shuffles:
 //
 //   predict_start tail   log_softmax (float64) over the C-1 non-MASK classes, -70 for MASK,
 //                        clamp [-70,0]                 categorical_diffusion/base.py:131-144
@@ -32,11 +32,19 @@ namespace ldm {
 //                              off the layout-resident kernels
 //   NL = 64, full vocabulary   one wavefront per token: the parity hooks that read or write (B, C, S) tensors
 //                              (ldm_posterior, ldm_sample_tokens), and vocabularies whose live set exceeds 48 (vanilla)
-template <int NL, bool LIVE, bool FAST>
+//
+// CMAX = the widest vocabulary an instantiation serves.  192 (the default): the forms above, as they always were.  576 (64 and
+// 128 bins per coordinate on the reference-precision engines, 9 classes per lane of a wavefront; f64 log-softmax only):
+//   NL = 64, LIVE              one wavefront per token, 3 slots per lane = live sets up to 192 (a 128-bin attribute has 130):
+//                              the step path.  The lane's share of the row — up to 9 logits — is loaded once, coalesced, the
+//                              log-softmax runs over all C - 1 classes, the posterior and the draw on the live ones
+//   NL = 64, full vocabulary   9 slots per lane, 576 scratch slots: the parity hooks, and vanilla (every class live)
+template <int NL, bool LIVE, bool FAST, int CMAX = 192>
 __global__ __launch_bounds__(256) void posterior_sample_k(PostArgs p) {
   constexpr int GPW = 64 / NL;            // tokens per wavefront
-  constexpr int NJ = LIVE ? 3 : 192 / NL; // class slots per lane
-  constexpr int NSC = LIVE ? 48 : 192;
+  constexpr int NJ = LIVE ? 3 : CMAX / NL; // class slots per lane
+  constexpr int NSC = LIVE ? 3 * NL : CMAX;
+  static_assert(CMAX == 192 || (CMAX == 576 && NL == 64 && !FAST), "wide vocabularies: one wavefront per token, f64 log-softmax");
   static_assert(LIVE || NL == 64, "full-vocabulary map: one wavefront per token");
   __shared__ float sh_lg[4 * GPW][NSC];
   __shared__ float sh_pr[4 * GPW][NSC];
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(256) void posterior_sample_k(PostArgs p) {
     // the three passes below used to re-read the row through a rolled loop — one dependent global load per iteration, ~10 exposed
     // L2 round trips per lane in front of the f64 exponentials: 111 us per launch in the split mode's profile, more than the
     // vocabulary head it follows).  Same values, same summation order: results are bit-identical.
-    constexpr int NX = (192 + NL - 1) / NL;   // ldm_create: at most 192 classes
+    constexpr int NX = (CMAX + NL - 1) / NL;  // ldm_create: at most CMAX classes reach this instantiation
     float xv[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
@@ -196,6 +204,15 @@ void launch_posterior_sample(const PostArgs& p, hipStream_t st) {
   for (int a = 0; a < p.v.n_attr; ++a) live_max = live_max > p.v.count[a] + 2 ? live_max : p.v.count[a] + 2;
   const char* fw = knob_env("LDM_POST_WAVE");  // A/B aid and test hook (read per launch: tests toggle it)
   const bool force_wave = fw && atoi(fw) != 0;
+  if (p.v.n_class > 192) {
+    // wide vocabularies (ldm_create: exact / split only, at most 576 classes, never the fp32 log-softmax): one wavefront per
+    // token either way — on the live classes (<= 192) for the step path, over the whole vocabulary for the (B, C, S) hooks
+    // and for vanilla
+    const bool full = p.logp_in || p.logp_out || live_max > 192 || force_wave;
+    auto kern = full ? posterior_sample_k<64, false, false, 576> : posterior_sample_k<64, true, false, 576>;
+    hipLaunchKernelGGL(kern, dim3((M + 3) / 4), dim3(256), 0, st, p);
+    return;
+  }
   const bool wave = p.logp_in || p.logp_out || live_max > 48 || force_wave;
   auto kern = wave ? (p.f32_lse ? posterior_sample_k<64, false, true> : posterior_sample_k<64, false, false>)
                    : (p.f32_lse ? posterior_sample_k<16, true, true> : posterior_sample_k<16, true, false>);

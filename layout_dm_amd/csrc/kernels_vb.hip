@@ -50,10 +50,13 @@ __global__ __launch_bounds__(256) void q_sample_k(VbArgs p) {
   p.xt_out[row] = ldm_vb::q_sample_token(a, x0, ns, (uint32_t)s, (uint32_t)p.t, p.first_layout + (uint64_t)b, p.seed);
 }
 
-template <int NL, bool LIVE, bool FAST>
+// CMAX: the widest vocabulary an instantiation serves, as in posterior_sample_k (192: the forms above; 576: one wavefront per token
+// on live sets up to 192, or over the whole vocabulary with 9 slots per lane — vanilla)
+template <int NL, bool LIVE, bool FAST, int CMAX = 192>
 __global__ __launch_bounds__(256) void vb_terms_k(VbArgs p) {
   constexpr int GPB = 256 / NL;           // tokens in flight per workgroup
-  constexpr int NJ = LIVE ? 3 : 192 / NL; // class slots per lane
+  constexpr int NJ = LIVE ? 3 : CMAX / NL; // class slots per lane
+  static_assert(CMAX == 192 || (CMAX == 576 && NL == 64 && !FAST), "wide vocabularies: one wavefront per token, f64 log-softmax");
   static_assert(LIVE || NL == 64, "full-vocabulary map: one wavefront per token");
   extern __shared__ float sh[];           // [kNumSums][S]
   const int b = blockIdx.x;
@@ -104,10 +107,16 @@ void launch_q_sample(const VbArgs& p, hipStream_t st) {
 void launch_vb_terms(const VbArgs& p, hipStream_t st) {
   int live_max = 0;
   for (int a = 0; a < p.v.n_attr; ++a) live_max = live_max > p.v.count[a] + 2 ? live_max : p.v.count[a] + 2;
+  const size_t lds = (size_t)ldm_vb::kNumSums * p.S * sizeof(float);
+  if (p.v.n_class > 192) {  // wide vocabularies (exact / split only): see launch_posterior_sample
+    auto kern = live_max > 192 ? vb_terms_k<64, false, false, 576> : vb_terms_k<64, true, false, 576>;
+    hipLaunchKernelGGL(kern, dim3(p.B), dim3(256), lds, st, p);
+    return;
+  }
   const bool wave = live_max > 48;
   auto kern = wave ? (p.f32_lse ? vb_terms_k<64, false, true> : vb_terms_k<64, false, false>)
                    : (p.f32_lse ? vb_terms_k<16, true, true> : vb_terms_k<16, true, false>);
-  hipLaunchKernelGGL(kern, dim3(p.B), dim3(256), (size_t)ldm_vb::kNumSums * p.S * sizeof(float), st, p);
+  hipLaunchKernelGGL(kern, dim3(p.B), dim3(256), lds, st, p);
 }
 
 }  // namespace ldm

@@ -38,8 +38,29 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
   if (cfg->n_attr != 5) return bad("only the c-x-y-w-h (5 attribute) vocabulary is supported");
   if (cfg->n_category < 1 || cfg->n_bin < 1 || cfg->n_layer < 1 || cfg->n_step < 1 || cfg->n_head < 1 || cfg->d_model < 16)
     return bad("n_category / n_bin / n_layer / n_step / n_head must be >= 1, d_model >= 16");
-  if (cfg->n_category + 4 * cfg->n_bin + 2 > 192)
-    return bad("vocabulary > 192 classes not supported by the fused posterior kernel");
+  {
+    // vocabulary: the fp16 engines (fast / mixed / hybrid) run the step tail on at most 192 classes (the stack kernel's fused tail, the
+    // 16-lane form of posterior_sample_k); the reference-precision engines (exact / split) have the wide forms of kernels_post.hip /
+    // kernels_vb.hip: 9 classes per lane of a wavefront = 576 classes = 18 head tiles, and the encode kernel's 128 bins (ldm_cond_core.h)
+    static thread_local char msg[256];
+    const long n_class = (long)cfg->n_category + 4L * cfg->n_bin + 2;
+    if (cfg->n_bin > 128) {
+      snprintf(msg, sizeof(msg), "n_bin = %d: more than 128 bins per coordinate are not supported", cfg->n_bin);
+      return bad(msg);
+    }
+    if (n_class > 576) {
+      snprintf(msg, sizeof(msg), "n_category + 4 * n_bin + 2 = %ld classes: vocabulary > 576 classes not supported", n_class);
+      return bad(msg);
+    }
+    const bool ref_prec = cfg_in->precision == LDM_PREC_EXACT_F32 || cfg_in->precision == LDM_PREC_SPLIT_F16;
+    if (n_class > 192 && !ref_prec) {
+      static const char* names[5] = {"exact", "fast", "split", "mixed", "hybrid"};
+      const char* nm = cfg_in->precision >= 0 && cfg_in->precision <= 4 ? names[cfg_in->precision] : "unknown";
+      snprintf(msg, sizeof(msg), "precision %s: vocabulary > 192 classes not supported by the fp16 engines (%ld classes); use precision split or exact",
+               nm, n_class);
+      return bad(msg);
+    }
+  }
   if (cfg->d_model % 16 || cfg->d_ff % 16 || cfg->d_model > 1024) return bad("d_model/d_ff must be multiples of 16, d_model <= 1024");
   if (cfg->d_model % cfg->n_head) return bad("d_model must be divisible by n_head");
   if (cfg->d_model / cfg->n_head > 64) return bad("head_dim > 64 not supported");
@@ -113,6 +134,9 @@ extern "C" int ldm_create(const ldm_config* cfg_in, int device, ldm_handle** out
   if (const char* ce = knob_env("LDM_CHUNK")) chunk = atoi(ce);  // experiments
   // auto: 256 layouts (M = 32 000 rows = 250 row blocks / 256 per-layout workgroups: one full round of the 256 CUs;
   // P + Q of a chunk = 119 MB stay inside the 256 MiB Infinity Cache) and two lanes (see Workspace)
+  // wide vocabularies (> 192 classes): a chunk's logits grow to chunk * S * Cp floats — 74 MB per lane at 576 classes, against 20 MB at
+  // 155 — and auto stays at 256 all the same: split at 283 / 539 classes, B = 512, T = 100 runs 1 171 / 1 158 layouts/s with 256-layout
+  // chunks, 1 125 / 1 108 with 128, 720 / 710 with 64 (tools/wide_vocab_bench.py --chunk, one session)
   if (chunk <= 0) chunk = 256;
   chunk = std::min(chunk, cfg->max_batch);
   h->chunk = chunk;

@@ -15,7 +15,8 @@
 //        DppGroup<16>      NL = 16  one DPP row: four tokens per wavefront (ldm_post_dpp.h) — the fused tail of the stack
 //                                   kernel (kernels_stack.hip) and posterior_sample_k's default form (kernels_post.hip)
 //        DppGroup<64>      NL = 64  one wavefront per token over the FULL vocabulary: the parity hooks that read or write
-//                                   (B, C, S) log-probability tensors (ldm_posterior / ldm_sample_tokens)
+//                                   (B, C, S) log-probability tensors (ldm_posterior / ldm_sample_tokens); above 192 classes
+//                                   also the step path, on the live classes (NJ = 3: live sets up to 192)
 //   M  (slot map)     SlotMap<NL, NJ, LIVE>: slot j of lane l is candidate l + NL j, in class order; LIVE = the candidates
 //                     are the token's live classes only, else all C classes.  A dead class carries exp(log(1e-30) / T) of
 //                     the mass at temperature T (1e-30 at T = 1): leaving the dead classes out of the draw is exact to
@@ -427,7 +428,10 @@ LDM_PT_HD Draw draw_token(const G& g, const M& m, const TokenArgs& a, float (&lp
 // ---- the one-lane form: log-softmax, posterior, overrides, draw on the token's live classes.  work: 2 * (count + 2)
 // floats of scratch (top-k / top-p).  F64_LSE: the reference's float64 log-softmax (exact mode); otherwise fp32 (fast).
 constexpr int kHostMaxLive = 64;
-template <bool F64_LSE>
+constexpr int kHostMaxLiveWide = 130;  // a 128-bin attribute: body + [PAD] + [MASK] (ldm_create: n_bin <= 128)
+// MAXLIVE: slots of the one lane — the token's live set must fit (kHostMaxLive: every vocabulary of at most 32 bins and 62
+// categories; kHostMaxLiveWide: the 64- and 128-bin vocabularies of the reference-precision engines)
+template <bool F64_LSE, int MAXLIVE = kHostMaxLive>
 LDM_PT_HD Draw step_token_draw(const TokenArgs& a, const StepSchedule& s, float* work) {
   const int C = a.n_class, K = a.count + 2;
   float mx = -INFINITY;
@@ -444,18 +448,18 @@ LDM_PT_HD Draw step_token_draw(const TokenArgs& a, const StepSchedule& s, float*
     lse0f = logf(se);
   }
   const HostLane g;
-  const SlotMap<1, kHostMaxLive, true> m{0};
-  float l0[kHostMaxLive], lp[kHostMaxLive];
-  for (int j = 0; j < kHostMaxLive; ++j) {
+  const SlotMap<1, MAXLIVE, true> m{0};
+  float l0[MAXLIVE], lp[MAXLIVE];
+  for (int j = 0; j < MAXLIVE; ++j) {
     l0[j] = 0.f;
     if (j < K - 1) l0[j] = F64_LSE ? l0_f64(a.logits[live_id(a, j)], mx, lse0d) : l0_f32(a.logits[live_id(a, j)], mx, lse0f);
   }
   token_log_probs(g, m, a, s, l0, lp);
   return draw_token(g, m, a, lp, work, work + K, true);
 }
-template <bool F64_LSE>
+template <bool F64_LSE, int MAXLIVE = kHostMaxLive>
 LDM_PT_HD int step_token(const TokenArgs& a, const StepSchedule& s, float* work) {
-  return step_token_draw<F64_LSE>(a, s, work).token;
+  return step_token_draw<F64_LSE, MAXLIVE>(a, s, work).token;
 }
 
 }  // namespace ldm_post

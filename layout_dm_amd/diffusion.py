@@ -22,6 +22,8 @@ from .binding import Engine
 _seed_counter = itertools.count()
 # the reference's entry point logs at INFO (trainer/test.py:38); `precision="auto"` says here which engine a checkpoint got and why
 logger = logging.getLogger("layout_dm_amd")
+
+FP16_MAX_CLASSES = 192   # ldm_create: fast / mixed / hybrid refuse wider vocabularies; exact / split take up to 576 classes, 128 bins
 # what each engine delivers on one MI355X (Rico25-shaped sequences, T = 100, batch 512; bench.py measures it on the box at hand)
 THROUGHPUT_CLASS = {
     "fast": "~3 900 layouts/s (fp16 operands, one launch per sampling call)",
@@ -118,7 +120,23 @@ class HipMaskAndReplaceDiffusion:
                                  d_model=d_model, n_head=n_head, d_ff=d_ff, n_layer=n_layer, n_step=num_timesteps,
                                  precision=prec, max_batch=mb, chunk=chunk, device=device, q_type=q_type,
                                  lanes=lanes)
-        if precision in ("fast_verified", "mixed_verified", "hybrid_verified", "auto"):
+        # wide vocabularies (64 / 128 bins per coordinate): the fp16 engines stop at FP16_MAX_CLASSES classes (ldm_create), the
+        # reference-precision engines at 576.  auto then IS its reference-precision engine — no fp16 engine is built or measured —
+        # and every name that needs an fp16 engine is refused with the library's own message
+        n_class = n_category + 4 * n_bin + 2
+        self.wide_vocab = n_class > FP16_MAX_CLASSES
+        if self.wide_vocab and precision != "auto" and precision not in ("exact", "split"):
+            try:
+                mk(precision[:-len("_verified")] if precision.endswith("_verified") else precision)
+            except RuntimeError as e:
+                if "192 classes" not in str(e):
+                    raise
+                raise NotImplementedError(str(e)) from e
+        if self.wide_vocab and self.auto:
+            assert verifier in ("split", "exact")
+            self.engine = mk(verifier)
+            self.selected_precision = verifier
+        elif precision in ("fast_verified", "mixed_verified", "hybrid_verified", "auto"):
             from .verified import VerifiedGreedy
 
             # the reference-precision engine behind fast_verified / mixed_verified / auto: "split" (fp16 x 3 on the fp16 matrix
@@ -290,6 +308,15 @@ class HipMaskAndReplaceDiffusion:
                     rep[rung + "_unavailable"] = err["unavailable"]
                 else:
                     rep[rung + "_logits_err_rel"] = err.get("err_rel")
+        if self.auto and self.wide_vocab:
+            rep.update({"n_class": self.num_classes, "fp16_max_classes": FP16_MAX_CLASSES,
+                        "reason": f"{self.num_classes} classes: the fp16 engines (fast / hybrid / mixed) serve at most {FP16_MAX_CLASSES}; "
+                                  "no fp16 engine was built or measured"})
+            self.selection_report = rep
+            logger.info("layout_dm_amd: precision='auto' selected engine '%s': the vocabulary has %d classes and the fp16 engines "
+                        "(fast / hybrid / mixed) serve at most %d — no fp16 engine was built; expect %s", sel, self.num_classes,
+                        FP16_MAX_CLASSES, rep["expected_throughput"])
+            return
         self.selection_report = rep
         if self.verified is None:
             logger.info("layout_dm_amd: engine '%s' (as requested) — %s", sel, rep["expected_throughput"])
