@@ -1,7 +1,9 @@
 // Development hooks of libldm_hip.so (NOT part of the public ABI in include/ldm_hip.h): the s_memtime phase sums of the instrumented
 // kernels (tools/phase_probe.py, lngemm_probe.py, attnout_probe.py) and a unit check of the fused attention + out_proj launch on
 // synthetic operands (tests/test_attnout_gpu.py), and one row-resident LayerNorm + GEMM launch of a live handle on the caller's rows
-// (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py).  Nothing in the product path calls into this file.
+// (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py), and one launch of a LayerNorm / GEMM / attention kernel of the tiled engines on the caller's
+// buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py).  Nothing in the product path calls
+// into this file.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -235,4 +237,152 @@ extern "C" int ldm_dev_lngemm_run(ldm_handle* h, const ldm_dev_lngemm_io* io) {
   HIP_OK(h, hipStreamSynchronize(0));
   HIP_OK(h, hipGetLastError());
   return 0;
+}
+
+// ONE launch of a kernel of the tiled engines (ldm_denoise.cpp denoise_chunk_tiled / denoise_chunk_fast) on the caller's device buffers, without
+// a handle: launch_layernorm, launch_gemm / launch_gemm16x3 / launch_gemm16, launch_attention / launch_attention16 (tests/test_tiled_kernels_gpu.py).
+// The io structs mirror LnArgs / GemmArgs / AttnArgs and carry the capacity of every buffer; no reference arithmetic here (tests/_tiled_cases.py
+// holds the float64 side).  -1, before any launch, for whatever the kernels' stated preconditions forbid — the kernels themselves check nothing;
+// the launch runs on the current device's null stream; -2 on a HIP error.
+namespace {
+
+bool aligned(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+int64_t whole_tiles(int n, int tile) { return (int64_t)((n + tile - 1) / tile) * tile; }
+int dev_launched() {
+  if (hipStreamSynchronize(0) != hipSuccess) return -2;
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+}  // namespace
+
+struct ldm_dev_layernorm_io {   // LnArgs
+  const float* x;
+  const int32_t* tokens;
+  const float *emb, *pos, *p0, *p1;
+  float* y32;
+  __half *y16, *y16lo;
+  float* stats_out;             // [M] (mean, rstd) pairs
+  int32_t M, D, S, ld16, ada, raw;
+  int64_t x_rows, n_tokens, emb_rows, pos_rows, n_p, y32_rows, y16_rows, stats_rows;   // capacities: rows of D (y16 / y16lo: of ld16) or elements
+};
+extern "C" int ldm_dev_layernorm_run(const ldm_dev_layernorm_io* io) {
+  if (!io) return -1;
+  const int M = io->M, D = io->D;
+  if (M < 1 || D < 4 || D % 4 || D > 1024) return -1;   // float4 per lane, at most ln_rows<4>'s 4 x 64 of them
+  if (io->tokens) {
+    if (!io->emb || !io->pos || io->S < 1 || io->n_tokens < M || io->pos_rows < std::min(M, io->S) || io->emb_rows < 1) return -1;
+    if (!aligned(io->emb, 16) || !aligned(io->pos, 16)) return -1;
+    std::vector<int32_t> tok(M);   // (the gather's row bound: the one check that needs the operand's values)
+    if (hipMemcpy(tok.data(), io->tokens, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+    for (int32_t t : tok)
+      if (t < 0 || t >= io->emb_rows) return -1;
+  } else if (!io->x || !aligned(io->x, 16) || io->x_rows < M) {
+    return -1;
+  }
+  if (io->raw) {
+    if (!io->y32) return -1;
+  } else {
+    if (!io->p0 || !io->p1 || !aligned(io->p0, 16) || !aligned(io->p1, 16) || io->n_p < D) return -1;
+    if (!io->y32 && !io->y16) return -1;
+  }
+  if (io->y32 && (!aligned(io->y32, 16) || io->y32_rows < M)) return -1;
+  if (io->y16lo && !io->y16) return -1;
+  if (io->y16 && (!aligned(io->y16, 8) || (io->y16lo && !aligned(io->y16lo, 8)) || io->ld16 < D || io->ld16 % 4 || io->y16_rows < M)) return -1;
+  if (io->stats_out && (!aligned(io->stats_out, 8) || io->stats_rows < M)) return -1;
+  LnArgs a{};
+  a.x = io->x; a.tokens = io->tokens; a.emb = io->emb; a.pos = io->pos; a.p0 = io->p0; a.p1 = io->p1;
+  a.y32 = io->y32; a.y16 = io->y16; a.y16lo = io->y16lo; a.stats_out = reinterpret_cast<float2*>(io->stats_out);
+  a.M = M; a.D = D; a.S = io->S; a.ld16 = io->ld16; a.ada = io->ada; a.raw = io->raw;
+  (void)hipGetLastError();
+  launch_layernorm(a, 0);
+  return dev_launched();
+}
+
+struct ldm_dev_gemm_io {        // GemmArgs + tag + kind
+  const void *A, *Alo, *W, *Wlo;
+  const float *bias, *res;
+  float* C32;
+  __half *C16, *C16lo;
+  int32_t M, N, K, lda, ldw, ldres, ldc32, ldc16, relu;
+  int32_t tag;                  // Linear class of the fp16 kernels (0 qkv, 1 attn_out, 2 ffn1, 3 ffn2, 4 head)
+  int32_t kind;                 // 0 launch_gemm (fp32) | 1 launch_gemm16x3 (fp16 hi / lo) | 2 launch_gemm16 (fp16)
+  float out_scale;
+  int64_t a_rows, w_rows, n_bias, res_rows, c32_rows, c16_rows;   // capacities: rows of the buffer's leading dimension, elements of bias
+};
+extern "C" int ldm_dev_gemm_run(const ldm_dev_gemm_io* io) {
+  if (!io) return -1;
+  const int M = io->M, N = io->N, K = io->K, kind = io->kind;
+  if (M < 1 || N < 1 || K < 1 || kind < 0 || kind > 2 || io->tag < 0 || io->tag > 4) return -1;
+  if (!io->A || !io->W || !aligned(io->A, 16) || !aligned(io->W, 16) || io->lda < K || io->ldw < K) return -1;   // 16-byte LDS-DMA segments
+  if (kind == 0) {
+    // gemm_f32_tile: 16-wide K tiles; rows past M / N are clamped to the last one, so M and N rows suffice; no out_scale in its epilogue
+    if (K % 16 || io->lda % 4 || io->ldw % 4 || io->a_rows < M || io->w_rows < N) return -1;
+    if (io->Alo || io->Wlo || (io->out_scale != 0.f && io->out_scale != 1.f)) return -1;
+  } else {
+    // gemm16x3_k / gemm16_k load whole tiles without a bounds check: 256 (x3, as launch_gemm16x3 states it) / 128 rows
+    const int tile = kind == 1 ? 256 : 128;
+    if (K % (kind == 1 ? 32 : kGemm16BK) || io->lda % 8 || io->ldw % 8) return -1;
+    if (io->a_rows < whole_tiles(M, tile) || io->w_rows < whole_tiles(N, tile)) return -1;
+    if (kind == 1 && (!io->Alo || !io->Wlo || !aligned(io->Alo, 16) || !aligned(io->Wlo, 16) || io->out_scale < 0.f)) return -1;
+    if (kind == 2 && (io->Alo || io->Wlo || io->C16lo || (io->out_scale != 0.f && io->out_scale != 1.f))) return -1;
+    if (N % 4 == 0) {   // their epilogues move 4 columns per access
+      if ((io->bias && !aligned(io->bias, 16)) || (io->res && (!aligned(io->res, 16) || io->ldres % 4)) ||
+          (io->C32 && (!aligned(io->C32, 16) || io->ldc32 % 4)) ||
+          (io->C16 && (!aligned(io->C16, 8) || io->ldc16 % 4 || (io->C16lo && !aligned(io->C16lo, 8)))))
+        return -1;
+    }
+  }
+  if (!io->C32 && !io->C16) return -1;
+  if (io->C16lo && !io->C16) return -1;
+  if (io->bias && io->n_bias < N) return -1;
+  if (io->res && (io->ldres < N || io->res_rows < M)) return -1;
+  if (io->C32 && (io->ldc32 < N || io->c32_rows < M)) return -1;
+  if (io->C16 && (io->ldc16 < N || io->c16_rows < M)) return -1;
+  GemmArgs g{};
+  g.A = io->A; g.Alo = io->Alo; g.W = io->W; g.Wlo = io->Wlo; g.bias = io->bias; g.res = io->res;
+  g.C32 = io->C32; g.C16 = io->C16; g.C16lo = io->C16lo;
+  g.M = M; g.N = N; g.K = K; g.lda = io->lda; g.ldw = io->ldw; g.ldres = io->ldres; g.ldc32 = io->ldc32; g.ldc16 = io->ldc16;
+  g.relu = io->relu; g.precision = kind == 0 ? LDM_PREC_EXACT_F32 : kind == 1 ? LDM_PREC_SPLIT_F16 : LDM_PREC_FAST_F16;
+  g.out_scale = io->out_scale;
+  (void)hipGetLastError();
+  if (kind == 0) launch_gemm(g, 0);
+  else if (kind == 1) launch_gemm16x3(g, io->tag, 0);
+  else launch_gemm16(g, io->tag, 0);
+  return dev_launched();
+}
+
+struct ldm_dev_attention_io {   // AttnArgs + kind
+  const void* qkv;
+  float* out32;
+  __half *out16, *out16lo;
+  int32_t in_f16, B, S, H, dh, D, ld, ldo32, ldo16;
+  int32_t kind;                 // 0 launch_attention | 1 launch_attention16 (head-padded fp16 layout: ld >= 3 H 64, ldo16 >= H 64; D is ignored)
+  int64_t qkv_rows, out32_rows, out16_rows;   // capacities in rows of ld / ldo32 / ldo16
+};
+extern "C" int ldm_dev_attention_run(const ldm_dev_attention_io* io) {
+  if (!io) return -1;
+  const int B = io->B, S = io->S, H = io->H, dh = io->dh;
+  if (B < 1 || S < 1 || H < 1 || dh < 1 || dh > 64 || (io->kind != 0 && io->kind != 1)) return -1;   // ldm_create: head_dim <= 64
+  const int64_t M = (int64_t)B * S;
+  if (M > (1 << 24) || !io->qkv || !aligned(io->qkv, 16) || io->qkv_rows < M) return -1;
+  if (io->kind == 1) {
+    // attn_mfma_k: one 128 x 128 score tile, 128-byte head rows read as 16-byte chunks, 8-byte stores
+    if (!io->in_f16 || S > 128 || io->out32 || io->out16lo || !io->out16 || !aligned(io->out16, 16)) return -1;
+    if (io->ld < 3 * H * 64 || io->ld % 8 || io->ldo16 < H * 64 || io->ldo16 % 8 || io->out16_rows < M) return -1;
+    (void)hipGetLastError();
+    launch_attention16(static_cast<const __half*>(io->qkv), io->out16, B, S, H, dh, io->ld, io->ldo16, 0);
+    return dev_launched();
+  }
+  if (io->D != H * dh || io->ld < 3 * io->D) return -1;
+  if ((size_t)2 * S * ((dh + 3) & ~3) * sizeof(float) > 160 * 1024) return -1;   // ldm_create: K and V of a (layout, head) in LDS
+  if (!io->out32 && !io->out16) return -1;
+  if (io->out16lo && !io->out16) return -1;
+  if (io->out32 && (!aligned(io->out32, 16) || io->ldo32 < io->D || io->out32_rows < M)) return -1;
+  if (io->out16 && (!aligned(io->out16, 16) || (io->out16lo && !aligned(io->out16lo, 16)) || io->ldo16 < io->D || io->out16_rows < M)) return -1;
+  AttnArgs a{};
+  a.qkv = io->qkv; a.in_f16 = io->in_f16; a.out32 = io->out32; a.out16 = io->out16; a.out16lo = io->out16lo;
+  a.B = B; a.S = S; a.H = H; a.dh = dh; a.D = io->D; a.ld = io->ld; a.ldo32 = io->ldo32; a.ldo16 = io->ldo16;
+  (void)hipGetLastError();
+  launch_attention(a, 0);
+  return dev_launched();
 }
