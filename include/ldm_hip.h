@@ -201,6 +201,25 @@ int ldm_vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, cons
 int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, uint64_t seed, uint64_t first_layout,
                 int B, double* d_sums, void* stream);
 
+/* ---- the same at a timestep PER LAYOUT, one denoiser pass for the whole call (additive exports, ABI 5) ------------
+ * The reference's forward() gives every layout of a batch its own t.  h_t: HOST array of B timesteps, as ldm_sample_loop takes
+ * h_t_model; a value outside [0, n_step) fails with -1 and names its index.  The array is read before the call returns and
+ * staged in a handle-owned device buffer of max_batch ints (allocated by the first such call: make that one outside a stream
+ * capture).  Row b of the result has the bits the single-t call at t = h_t[b] gives row b of the same batch: only the AdaLN
+ * parameters, the schedule rows and the Philox counter depend on t, and each takes the row's value.
+ * h_layout: NULL, or B host values — the layout index in the Philox key of row b is first_layout + (h_layout ? h_layout[b] : b),
+ * so that one layout may stand in several rows of a call, at several t, and still draw what
+ * ldm_q_sample(.., t, seed, first_layout + its index, ..) draws for it.
+ * Token checks and the error-word read-back as above.  -4: the handle's denoiser has no per-layout form — LDM_PREC_FAST_F16 on
+ * the reference's backbone (the stack kernel); ldm_describe reports per_layout_t=0|1. */
+int ldm_denoise_logits_t(ldm_handle* h, const int32_t* d_tokens, const int32_t* h_t, int B, float* d_logits, void* stream);
+int ldm_q_sample_t(ldm_handle* h, const int32_t* d_x0, const int32_t* h_t, const uint64_t* h_layout, uint64_t seed,
+                   uint64_t first_layout, int B, int32_t* d_xt, void* stream);
+int ldm_vb_terms_t(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, int B,
+                   double* d_sums, float* d_tok, void* stream);
+int ldm_vb_step_t(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, const uint64_t* h_layout,
+                  uint64_t seed, uint64_t first_layout, int B, double* d_sums, void* stream);
+
 /* ---- near-tie report of deterministic decoding (ABI 4; tie_abs: ABI 5) ------------------------
  * north star: "token indices bit-exact under greedy/argmax decoding".  LDM_PREC_FAST_F16's logits carry an error that
  * depends on the checkpoint (3e-4 of max |logit| on the reference's init, 1e-3 on wider weights, more once attention rows

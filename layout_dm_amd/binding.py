@@ -46,6 +46,8 @@ EXPORTS = (
     "ldm_nearest_centre", "ldm_dev_cluster_stages",
     # scoring given layouts (Engine.q_sample / vb_terms / vb_step)
     "ldm_q_sample", "ldm_vb_terms", "ldm_vb_step",
+    # ... at a timestep per layout (Engine.denoise_logits_t / q_sample_t / vb_terms_t / vb_step_t)
+    "ldm_denoise_logits_t", "ldm_q_sample_t", "ldm_vb_terms_t", "ldm_vb_step_t",
 )
 
 
@@ -162,6 +164,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_q_sample.argtypes = [vp, vp, i32, u64, u64, i32, vp, vp]
     lib.ldm_vb_terms.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
     lib.ldm_vb_step.argtypes = [vp, vp, vp, i32, u64, u64, i32, vp, vp]
+    lib.ldm_denoise_logits_t.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.ldm_q_sample_t.argtypes = [vp, vp, vp, vp, u64, u64, i32, vp, vp]
+    lib.ldm_vb_terms_t.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.ldm_vb_step_t.argtypes = [vp, vp, vp, vp, vp, u64, u64, i32, vp, vp]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int
@@ -407,6 +413,88 @@ class Engine:
         self._check_tokens(self.lib.ldm_vb_step(self._h, x0.data_ptr(), xt.data_ptr() if xt is not None else None, int(t),
                                                 int(seed), int(first_layout), B, out.data_ptr(), _stream_ptr(self.device)),
                            "ldm_vb_step")
+        return out
+
+    # ------------------------------------------------------------------ ... at a timestep per layout
+    @property
+    def per_layout_t(self) -> bool:
+        """This engine's denoiser takes a timestep per layout (ldm_describe per_layout_t): every engine but `fast` on the
+        reference's backbone, whose stack kernel takes one set of AdaLN rows per launch.  Where it is False the *_t calls
+        raise (rc -4)."""
+        if getattr(self, "_per_layout_t", None) is None:
+            self._per_layout_t = self.describe().get("per_layout_t", "0") == "1"
+        return self._per_layout_t
+
+    def _host_t(self, t, B: int):
+        """(B,) timesteps -> a host int32 array the call reads before it returns (the library checks the range)"""
+        t = np.ascontiguousarray(torch.as_tensor(t).cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t), dtype=np.int32).reshape(-1)
+        if t.size != B:
+            raise ValueError(f"t must hold {B} timesteps, one per layout; got {t.size}")
+        return t
+
+    def _host_layout(self, layout, B: int):
+        if layout is None:
+            return None
+        layout = np.ascontiguousarray(torch.as_tensor(layout).cpu().numpy() if isinstance(layout, torch.Tensor) else np.asarray(layout),
+                                      dtype=np.uint64).reshape(-1)
+        if layout.size != B:
+            raise ValueError(f"layout must hold {B} layout indices, one per row; got {layout.size}")
+        return layout
+
+    def denoise_logits_t(self, tokens: torch.Tensor, t) -> torch.Tensor:
+        """denoise_logits with t (B,) per-layout timesteps in one pass: row b has the bits of denoise_logits(tokens, t[b])[b]."""
+        tokens = self._tok(tokens)
+        B = tokens.shape[0]
+        ht = self._host_t(t, B)
+        out = torch.empty((B, self.S, self.C), dtype=torch.float32, device=self.device)
+        self._check(self.lib.ldm_denoise_logits_t(self._h, tokens.data_ptr(), ht.ctypes.data_as(C.c_void_p), B, out.data_ptr(),
+                                                  _stream_ptr(self.device)), "ldm_denoise_logits_t")
+        return out
+
+    def q_sample_t(self, x0: torch.Tensor, t, seed: int = 0, first_layout: int = 0, layout=None) -> torch.Tensor:
+        """q_sample with t (B,) per-layout timesteps.  layout (B,) or None: the layout index of row b in the Philox key is
+        first_layout + (layout[b] if given, else b) — row b equals q_sample(x0, t[b], seed, first_layout)[layout[b] or b]
+        wherever x0's row is that layout's."""
+        x0 = self._tok(x0)
+        B = x0.shape[0]
+        ht, hl = self._host_t(t, B), self._host_layout(layout, B)
+        out = torch.empty_like(x0)
+        self._check_tokens(self.lib.ldm_q_sample_t(self._h, x0.data_ptr(), ht.ctypes.data_as(C.c_void_p),
+                                                   hl.ctypes.data_as(C.c_void_p) if hl is not None else None, int(seed), int(first_layout),
+                                                   B, out.data_ptr(), _stream_ptr(self.device)), "ldm_q_sample_t")
+        return out
+
+    def vb_terms_t(self, logits: torch.Tensor, x0: torch.Tensor, xt: torch.Tensor, t, per_token: bool = False):
+        """vb_terms with t (B,) per-layout timesteps: row b has the bits of vb_terms(.., t[b])[b]."""
+        x0, xt = self._tok(x0), self._tok(xt)
+        B = x0.shape[0]
+        assert xt.shape == x0.shape == (B, self.S) and tuple(logits.shape) == (B, self.S, self.C)
+        ht = self._host_t(t, B)
+        logits = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        sums = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        tok = torch.empty((3, B, self.S), dtype=torch.float32, device=self.device) if per_token else None
+        self._check_tokens(self.lib.ldm_vb_terms_t(self._h, logits.data_ptr(), x0.data_ptr(), xt.data_ptr(), ht.ctypes.data_as(C.c_void_p),
+                                                   B, sums.data_ptr(), tok.data_ptr() if per_token else None,
+                                                   _stream_ptr(self.device)), "ldm_vb_terms_t")
+        return (sums, tok) if per_token else sums
+
+    def vb_step_t(self, x0: torch.Tensor, t, xt: Optional[torch.Tensor] = None, seed: int = 0, first_layout: int = 0,
+                  layout=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """vb_step with t (B,) per-layout timesteps (and layout (B,) Philox layout indices, see q_sample_t): ONE denoiser pass per
+        chunk for layouts at different t; (B,4) float64 sums, row b with the bits of vb_step(.., t[b])[b]."""
+        x0 = self._tok(x0)
+        B = x0.shape[0]
+        ht, hl = self._host_t(t, B), self._host_layout(layout, B)
+        if xt is not None:
+            xt = self._tok(xt)
+            assert xt.shape == x0.shape
+        if out is None:
+            out = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        assert out.shape == (B, 4) and out.dtype == torch.float64 and out.is_contiguous() and out.device == self.device
+        self._check_tokens(self.lib.ldm_vb_step_t(self._h, x0.data_ptr(), xt.data_ptr() if xt is not None else None,
+                                                  ht.ctypes.data_as(C.c_void_p), hl.ctypes.data_as(C.c_void_p) if hl is not None else None,
+                                                  int(seed), int(first_layout), B, out.data_ptr(), _stream_ptr(self.device)),
+                           "ldm_vb_step_t")
         return out
 
     # ------------------------------------------------------------------ hot path

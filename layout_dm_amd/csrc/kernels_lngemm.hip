@@ -555,11 +555,25 @@ __device__ __forceinline__ void lp_step(LpState& s, f32x16* accs, int stage) {
 
 }  // namespace
 
+// (PLT) 1 + AdaLN scale of four columns, in fp32 like the staging loop of the single-t forms
+__device__ __forceinline__ float4 plt_multiplier(const float* scale) {
+  const float4 sc = *reinterpret_cast<const float4*>(scale);
+  return make_float4(1.0f + sc.x, 1.0f + sc.y, 1.0f + sc.z, 1.0f + sc.w);
+}
+
 // NPM / NPP: products per k16-step of the tile loop / of the GEMM prologue — 3 (split), 2 (weights fp16 only), 1 (plain fp16: the activation
 // operand has no lo half either)
+// Per-layout timesteps (LnGemmArgs.t_rows; ADA only): bit LG_PLT of the variant argument ABL.  It is no measurement variant — a product form
+// like the others, launched by ldm_*_t — but it travels in that argument so that the single-t forms <.., TM = false, ABL = 0, ..> keep their
+// names, which the static checks identify them by, and with the names their code: every line the bit adds is an `if constexpr`.
+// A 128-row block spans several layouts (up to 3 at S = 125, more for short sequences), so no parameter set is staged: every lane
+// reads the scale / shift of ITS row's layout from the AdaLN table in global memory at the normalisation step (a wavefront's 32
+// rows share one or two table rows: L1 / L2 hits), and forms the multiplier as 1.0f + scale in fp32 like the staging loop does.
+constexpr int LG_PLT = 256;
 template <bool ADA, int OUT, bool TM = false, int ABL = 0, bool PRE = false, int NPM = 3, int NPP = 3>
 __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
-  constexpr bool W2 = NPM < 3, W2P = NPP < 3;
+  constexpr bool W2 = NPM < 3, W2P = NPP < 3, PLT = (ABL & LG_PLT) != 0;
+  static_assert(!PLT || (ADA && !TM && ABL == LG_PLT), "per-layout timesteps select AdaLN parameters; no measurement variant of that form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long t_k0 = 0, t_pro = 0, t_loop = 0;
   if constexpr (TM) t_k0 = __builtin_amdgcn_s_memtime();
@@ -571,11 +585,12 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   float* sbias = reinterpret_cast<float*>(smem + LG_BIAS_OFF);
 
   // ---- parameter tables -> LDS: multiplier | shift (zero beyond D: padded columns come out as exact zeros), bias
-  for (int i = tid; i < 512; i += 256) {
-    const bool in = i < a.D;
-    spar[i] = in ? (ADA ? 1.0f + a.p0[i] : a.p0[i]) : 0.f;
-    spar[512 + i] = in ? a.p1[i] : 0.f;
-  }
+  if constexpr (!PLT)
+    for (int i = tid; i < 512; i += 256) {
+      const bool in = i < a.D;
+      spar[i] = in ? (ADA ? 1.0f + a.p0[i] : a.p0[i]) : 0.f;
+      spar[512 + i] = in ? a.p1[i] : 0.f;
+    }
   for (int i = tid; i < a.n_tiles * 32; i += 256) sbias[i] = (a.bias && i < a.N) ? a.bias[i] : 0.f;
   constexpr int NG = 58;
   const int row = blockIdx.x * 128 + wave * 32 + r;
@@ -702,14 +717,17 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   // fragment takes the place of the raw values it was made from (v[] dies pair by pair), the lo fragment goes to AGPRs.
   f16x8 xhi[LG::KS], xlo[LG::KS];
   float* yrow = (ADA && a.y32) ? a.y32 + (size_t)rrow * a.D + hi * 4 : nullptr;
+  // (PLT) the scale of this lane's row at its layout's timestep, + hi * 4; the shift D floats behind it (D == 464 = 58 groups: no pad columns)
+  const float* prow = nullptr;
+  if constexpr (PLT) prow = a.ada_tab + (size_t)a.t_rows[rrow / a.S] * a.t_stride + a.layer_off + hi * 4;
 #pragma unroll
   for (int ks = 0; ks < LG::KS; ++ks) {
     f16x8 fh, fl;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int g = 2 * ks + u;
-      const float4 gm = *reinterpret_cast<const float4*>(spar + g * 8 + hi * 4);
-      const float4 sh = *reinterpret_cast<const float4*>(spar + 512 + g * 8 + hi * 4);
+      const float4 gm = PLT ? plt_multiplier(prow + g * 8) : *reinterpret_cast<const float4*>(spar + g * 8 + hi * 4);
+      const float4 sh = *reinterpret_cast<const float4*>(PLT ? prow + a.D + g * 8 : spar + 512 + g * 8 + hi * 4);
       float4 y;
       y.x = (v[g].x - mean) * rstd * gm.x + sh.x;
       y.y = (v[g].y - mean) * rstd * gm.y + sh.y;
@@ -785,7 +803,7 @@ __global__ __launch_bounds__(256, 1) void lngemm16x3_k(LnGemmArgs a) {
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   if constexpr (TM) t_pro = __builtin_amdgcn_s_memtime();
-  if constexpr (ABL != 0) {   // (timing variants: whatever they leave unwritten starts defined)
+  if constexpr ((ABL & ~LG_PLT) != 0) {   // (timing variants: whatever they leave unwritten starts defined)
     for (int k = 0; k < 16; ++k) s.accA[k] = s.accB[k] = 0.f;
     for (int k = 0; k < LG::PF; ++k) s.qh[k] = s.ql[k] = xhi[k];
   }
@@ -874,10 +892,25 @@ int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st) {
     else if (head) kern = pre ? lngemm16x3_k<false, 0, false, 0, true, 1, 1> : lngemm16x3_k<false, 0, false, 0, false, 1, 1>;
   }
   if (!kern) return -1;
-  if (tm && npm == 3 && !pre && !panel) kern = a.ada ? lngemm16x3_k<true, 0, true> : lngemm16x3_k<false, 1, true>;   // (in_proj under LDM_X3_ATTNOUT=0, linear1)
+  // per-layout timesteps: the seven in_proj forms above (ADA = 1) with the LG_PLT bit — <1, OUT, 0, LG_PLT, PRE, NPM, NPP>
+  const bool plt = a.t_rows != nullptr;
+  if (plt) {
+    if (!a.ada || !a.ada_tab || a.S <= 0 || a.t_stride < 2 * a.D || a.layer_off < 0) return -1;
+    kern = nullptr;
+    if (npm == 3 && npp == 3) {
+      if (panel) kern = pre ? lngemm16x3_k<true, 2, false, LG_PLT, true, 3, 3> : lngemm16x3_k<true, 2, false, LG_PLT, false, 3, 3>;
+      else if (!half_out) kern = pre ? lngemm16x3_k<true, 0, false, LG_PLT, true, 3, 3> : lngemm16x3_k<true, 0, false, LG_PLT, false, 3, 3>;
+    } else if (npm == 2 && npp == 2) {
+      if (panel) kern = pre ? lngemm16x3_k<true, 2, false, LG_PLT, true, 2, 2> : lngemm16x3_k<true, 2, false, LG_PLT, false, 2, 2>;
+    } else if (npm == 2 && npp == 1) {
+      if (panel && pre) kern = lngemm16x3_k<true, 2, false, LG_PLT, true, 2, 1>;
+    }
+    if (!kern) return -1;
+  }
+  if (tm && !plt && npm == 3 && !pre && !panel) kern = a.ada ? lngemm16x3_k<true, 0, true> : lngemm16x3_k<false, 1, true>;   // (in_proj under LDM_X3_ATTNOUT=0, linear1)
 #ifdef LDM_LNGEMM_ABL_BUILD   // measurement build (tools/build_measurement_variants.py lngemm): compile-time timing variants of the loop
   static const int abl_knob = (int)knob_int("LDM_LNGEMM_ABL", 0);
-  const int abl = (pre || panel || hi_only || npm != 3) ? 0 : abl_knob;
+  const int abl = (pre || panel || hi_only || npm != 3 || plt) ? 0 : abl_knob;
 #define LG_ABL(n) case n: kern = a.ada ? lngemm16x3_k<true, 0, false, n> : lngemm16x3_k<false, 1, false, n>; break;
   switch (abl) { LG_ABL(2) LG_ABL(4) LG_ABL(8) LG_ABL(6) LG_ABL(10) LG_ABL(12) LG_ABL(14) LG_ABL(16) LG_ABL(32) LG_ABL(64) default: break; }
 #undef LG_ABL

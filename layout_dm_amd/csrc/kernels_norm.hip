@@ -75,6 +75,11 @@ __global__ __launch_bounds__(256) void ln_rows(LnArgs a) {
   }
   const float4* p0 = reinterpret_cast<const float4*>(a.p0);
   const float4* p1 = reinterpret_cast<const float4*>(a.p1);
+  if (a.t_rows) {  // per-layout timesteps: the AdaLN rows of this row's layout (uniform over the wavefront: one row per wave)
+    const float* ss = a.ada_tab + (size_t)a.t_rows[row / a.S] * a.t_stride + a.layer_off;
+    p0 = reinterpret_cast<const float4*>(ss);
+    p1 = reinterpret_cast<const float4*>(ss + a.D);
+  }
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = i * 64 + lane;

@@ -10,6 +10,8 @@
 //                The group's lane 0 leaves the token's kl / nll / aux / hit in LDS; after one barrier four lanes add a
 //                quantity each over the positions, left to right, in float64.  No floating-point atomics: two runs give
 //                the same bits, and a layout's sums do not depend on the batch around it.
+// Per-layout timesteps (VbArgs.t_rows / layout_rows, the ldm_*_t entry points): the schedule rows and the Philox key take the
+// layout's own t and layout index (ldm_vb_core.h row_t / row_layout); nullptr: the call's single t and the row position.
 #include "ldm_kernels.h"
 #include "ldm_post_dpp.h"
 #include "ldm_vb_core.h"
@@ -46,8 +48,9 @@ __global__ __launch_bounds__(256) void q_sample_k(VbArgs p) {
     p.xt_out[row] = p.xt[row];
     return;
   }
-  const ldm_vb::NoiseSchedule ns = ldm_vb::noise_schedule(p.sched, p.v.n_attr, attr, p.T, p.t);
-  p.xt_out[row] = ldm_vb::q_sample_token(a, x0, ns, (uint32_t)s, (uint32_t)p.t, p.first_layout + (uint64_t)b, p.seed);
+  const int t = ldm_vb::row_t(p.t_rows, p.t, b);
+  const ldm_vb::NoiseSchedule ns = ldm_vb::noise_schedule(p.sched, p.v.n_attr, attr, p.T, t);
+  p.xt_out[row] = ldm_vb::q_sample_token(a, x0, ns, (uint32_t)s, (uint32_t)t, ldm_vb::row_layout(p.first_layout, p.layout_rows, b), p.seed);
 }
 
 // CMAX: the widest vocabulary an instantiation serves, as in posterior_sample_k (192: the forms above; 576: one wavefront per token
@@ -61,6 +64,7 @@ __global__ __launch_bounds__(256) void vb_terms_k(VbArgs p) {
   extern __shared__ float sh[];           // [kNumSums][S]
   const int b = blockIdx.x;
   const int S = p.S;
+  const int t_b = ldm_vb::row_t(p.t_rows, p.t, b);   // (uniform: one workgroup per layout)
   const int grp = threadIdx.x / NL;
   const ldm_post::DppGroup<NL, FAST> g{(int)threadIdx.x % NL};
   const ldm_post::SlotMap<NL, NJ, LIVE> m{(int)threadIdx.x % NL};
@@ -76,7 +80,7 @@ __global__ __launch_bounds__(256) void vb_terms_k(VbArgs p) {
     if (e) {
       if (g.lane() == 0) atomicOr(p.err, e);
     } else {
-      t = ldm_vb::token_terms<!FAST>(g, m, a, x0, ldm_vb::step_schedule(p.sched, p.v.n_attr, attr, p.T, p.t));
+      t = ldm_vb::token_terms<!FAST>(g, m, a, x0, ldm_vb::step_schedule(p.sched, p.v.n_attr, attr, p.T, t_b));
     }
     if (g.lane() == 0) {
       sh[ldm_vb::kSumKl * S + s] = t.kl;

@@ -336,6 +336,44 @@ extern "C" int ldm_denoise_logits(ldm_handle* h, const int32_t* d_tokens, int t,
   return 0;
 }
 
+// Per-layout timesteps of a call: checked on the host, copied to a pageable array of the handle's (an upload from pageable memory has
+// read its source when it returns, so neither the caller's array nor a following call's copy can race it) and uploaded on `st`.
+int ldm_host::stage_timesteps(ldm_handle* h, const int32_t* h_t, int B, hipStream_t st, const int32_t** d_t) {
+  if (!h_t) return h->fail(-1, "null argument");
+  if (!per_layout_t(h))
+    return h->fail(-4, "per-layout timesteps: precision fast_f16 on the stack kernel has no per-layout form (ldm_describe per_layout_t=0)");
+  for (int b = 0; b < B; ++b)
+    if (h_t[b] < 0 || h_t[b] >= h->T) return h->fail(-1, "timestep %d of layout %d out of range [0,%d)", h_t[b], b, h->T);  // constrained.py:139
+  if (!h->st_t) {
+    int rc = h->dalloc(&h->st_t, (size_t)h->cfg.max_batch);
+    if (rc) return rc;
+    h->st_t_host.resize((size_t)h->cfg.max_batch);
+  }
+  std::copy(h_t, h_t + B, h->st_t_host.begin());
+  HIP_OK(h, hipMemcpyAsync(h->st_t, h->st_t_host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  *d_t = h->st_t;
+  return 0;
+}
+
+extern "C" int ldm_denoise_logits_t(ldm_handle* h, const int32_t* d_tokens, const int32_t* h_t, int B, float* d_logits, void* stream) {
+  int rc = check_ready(h, B);
+  if (rc) return rc;
+  if (!d_tokens || !d_logits) return h->fail(-1, "null argument");
+  ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* d_t = nullptr;
+  if ((rc = stage_timesteps(h, h_t, B, st, &d_t))) return rc;
+  Workspace& ws = h->ws[0];
+  for (int off = 0; off < B; off += h->chunk) {
+    const int Bc = std::min(h->chunk, B - off);
+    if ((rc = denoise_chunk(h, ws, d_tokens + (size_t)off * h->S, 0, Bc, st, false, d_t + off))) return rc;
+    HIP_OK(h, hipMemcpy2DAsync(d_logits + (size_t)off * h->S * h->C, (size_t)h->C * 4, ws.logits, (size_t)h->Cp * 4,
+                               (size_t)h->C * 4, (size_t)Bc * h->S, hipMemcpyDeviceToDevice, st));
+  }
+  HIP_OK(h, hipGetLastError());
+  return 0;
+}
+
 extern "C" int ldm_posterior(ldm_handle* h, const float* d_logits, const int32_t* d_tokens, int t_post, int B,
                              const ldm_cond* cond, float* d_logp, void* stream) {
   int rc = check_ready(h, B);
@@ -496,6 +534,8 @@ extern "C" int ldm_describe(const ldm_handle* h, char* buf, int cap) {
   s += std::string(";step0_cache=") + (loop && h->step0_cache && h->step0_tab ? "on" : "off") + ";step0_entries=";
   for (size_t i = 0; i < h->step0.size(); ++i)
     s += (i ? "," : "") + std::to_string(h->step0[i].t) + ":" + std::to_string(h->step0[i].S);
+  // the denoiser takes per-layout timesteps (ldm_denoise_logits_t, ldm_vb_step_t): every engine but fast_f16 on the stack kernel
+  s += std::string(";per_layout_t=") + (per_layout_t(h) ? "1" : "0");
   s += ";knobs=" + knobs_honoured();
   if (buf && cap > 0) {
     const size_t n = std::min((size_t)cap - 1, s.size());

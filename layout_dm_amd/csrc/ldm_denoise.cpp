@@ -1,6 +1,9 @@
 // Host side of libldm_hip.so: the launch sequence of ONE denoiser pass over a chunk of layouts, per numerics mode
 // (CategoricalTransformer.forward, nn_lib.py:191-237 + transformer_utils.py:165-246).  One function per engine structure, each the
 // launch list of that engine from top to bottom; denoise_chunk (last) picks among them.
+// Per-layout timesteps (the ldm_*_t entry points): d_t, a device array of the chunk's Bc timesteps, or nullptr — then every layout runs
+// at t, today's code.  With d_t the AdaLN launches take each row's parameters from the table at its layout's timestep (LnArgs /
+// LnGemmArgs t_rows); nothing else of a pass depends on t.
 #include "ldm_handle.h"
 #include "ldm_pack.h"
 
@@ -13,11 +16,13 @@ static double attention_flops(const ldm_handle* h, int Bc) { return 4.0 * Bc * h
 // ------------------------------------------------------------------------------------------ the two launch helpers
 // One LayerNorm launch (kernels_norm.hip) over x [M, D]: AdaLN (p0 / p1 = scale / shift; with `tokens`, x = emb[token] + pos first) or
 // nn.LayerNorm (gamma / beta), into whichever of y32 / y16 / y16lo the mode keeps (the others nullptr); ld16 = width of the fp16 rows
+// d_t / layer (ada only): per-layout timesteps — the parameters of row m are the AdaLN table's at (d_t[m / S], layer)
 static void layernorm(ldm_handle* h, hipStream_t st, const char* name, int M, const float* x, const int32_t* tokens, const float* p0,
-                      const float* p1, int ada, float* y32, __half* y16, __half* y16lo, int ld16) {
+                      const float* p1, int ada, float* y32, __half* y16, __half* y16lo, int ld16, const int32_t* d_t = nullptr, int layer = 0) {
   LnArgs a{};
   a.x = x; a.tokens = tokens; a.emb = h->emb; a.pos = h->pos;
   a.p0 = p0; a.p1 = p1; a.ada = ada;
+  if (ada && d_t) { a.t_rows = d_t; a.ada_tab = h->adaln; a.t_stride = h->L * 2 * h->D; a.layer_off = layer * 2 * h->D; }
   a.y32 = y32; a.y16 = y16; a.y16lo = y16lo;
   a.M = M; a.D = h->D; a.S = h->S; a.ld16 = ld16;
   ldm_handle::Scope sc(h, st, name, 0, (double)M * h->D * (4 + (y32 ? 4 : 0) + (y16 ? 2 : 0)));
@@ -88,7 +93,7 @@ static int denoise_chunk_stack(ldm_handle* h, Workspace& ws, const int32_t* d_to
 
 // ------------------------------------------------------------------------------------------ fast, every other accepted geometry
 // fp16 LDS-DMA GEMMs + MFMA attention on the head-padded layout
-static int denoise_chunk_fast(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st) {
+static int denoise_chunk_fast(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, const int32_t* d_t) {
   const int M = Bc * h->S, D = h->D, F = h->F, C = h->C, Dq = h->Dq, HD = h->HD, Fq = h->Fq;
   auto gemm = [&](const char* name, int tag, const __half* A, int lda, int K, const __half* W, int ldw, int N,
                   const float* bias, int relu, const float* res, float* C32, int ldc32, __half* C16, int ldc16,
@@ -104,7 +109,7 @@ static int denoise_chunk_fast(ldm_handle* h, Workspace& ws, const int32_t* d_tok
     const LayerW& w = h->layers[i];
     const ldm_handle::FastLayer& f = h->fast[i];
     const float* ss = h->adaln + ((size_t)t * h->L + i) * 2 * D;
-    layernorm(h, st, i == 0 ? "embed_adaln" : "adaln", M, ws.P, i == 0 ? d_tokens : nullptr, ss, ss + D, 1, ws.P, ws.a16, nullptr, Dq);
+    layernorm(h, st, i == 0 ? "embed_adaln" : "adaln", M, ws.P, i == 0 ? d_tokens : nullptr, ss, ss + D, 1, ws.P, ws.a16, nullptr, Dq, d_t, i);
     gemm("gemm_qkv", 0, ws.a16, Dq, D, f.w_in, Dq, 3 * HD, f.b_in, 0, nullptr, nullptr, 0, ws.qkv16,
          3 * HD, gemm_flops(M, 3 * D, D), (double)M * (D * 2 + 3 * HD * 2));
     {
@@ -145,13 +150,13 @@ static int attention_out_proj(ldm_handle* h, Workspace& ws, const LayerW& w, int
 
 // LayerNorm launch -> GEMM -> attention -> GEMM -> LayerNorm -> GEMM -> GEMM per block, then the head.  Every activation exists once, in
 // the form of its mode (the Workspace members of the other form are nullptr, and so are the fp16 weight copies in the exact mode).
-static int denoise_chunk_tiled(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st) {
+static int denoise_chunk_tiled(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, const int32_t* d_t) {
   const int M = Bc * h->S, D = h->D, F = h->F, Dp = h->Dp, Fp = h->Fp;
   for (int i = 0; i < h->L; ++i) {
     const LayerW& w = h->layers[i];
     const float* ss = h->adaln + ((size_t)t * h->L + i) * 2 * D;
     // AdaLN (layer 0: fused with the embedding gather); P <- normed x (the residual base)
-    layernorm(h, st, i == 0 ? "embed_adaln" : "adaln", M, ws.P, i == 0 ? d_tokens : nullptr, ss, ss + D, 1, ws.P, ws.a16, ws.a16lo, Dp);
+    layernorm(h, st, i == 0 ? "embed_adaln" : "adaln", M, ws.P, i == 0 ? d_tokens : nullptr, ss, ss + D, 1, ws.P, ws.a16, ws.a16lo, Dp, d_t, i);
     if (int rc = tiled_gemm(h, st, "gemm_qkv", 0, M, 3 * D, D, Dp, {ws.P, ws.a16, ws.a16lo}, {w.w_in, w.w_in16, w.w_in16lo, w.s_in}, w.b_in, 0,
                             nullptr, ws.qkv32, 3 * D))
       return rc;
@@ -187,7 +192,8 @@ static void ffn2_prologue(const ldm_handle* h, const Workspace& ws, const LayerW
 
 // AdaLN of layer i at timestep t (layer 0: fused with the embedding gather) + QKV projection; P <- normed x (the residual base).
 // pre: x = Q + hid · W2^T + b2 of the PREVIOUS layer, computed in this launch (never stored)
-LnGemmArgs ldm_host::lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre) {
+LnGemmArgs ldm_host::lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre,
+                                         const int32_t* d_t) {
   const int D = h->D;
   const LayerW& w = h->layers[i];
   const float* ss = h->adaln + ((size_t)t * h->L + i) * 2 * D;
@@ -196,6 +202,7 @@ LnGemmArgs ldm_host::lngemm_in_proj_args(const ldm_handle* h, const Workspace& w
   a.tokens = (i == 0) ? d_tokens : nullptr;
   a.emb = h->emb; a.pos = h->pos; a.S = h->S;
   a.p0 = ss; a.p1 = ss + D; a.ada = 1;
+  if (d_t) { a.t_rows = d_t; a.ada_tab = h->adaln; a.t_stride = h->L * 2 * D; a.layer_off = i * 2 * D; }   // per-layout timesteps: p0 / p1 are not read
   a.y32 = ws.P;
   a.out_scale = w.s_in;
   a.M = M; a.D = D; a.np_main = h->np_w;
@@ -244,14 +251,14 @@ LnGemmArgs ldm_host::lngemm_head_args(const ldm_handle* h, const Workspace& ws, 
 // The LayerNorm-fed GEMMs as ONE row-resident launch each (kernels_lngemm.hip), attention + out_proj as one layout-resident launch
 // (kernels_attnout.hip).  linear2 has no launch of its own: it runs as the GEMM prologue of the next in_proj / of the head — or, in the
 // hybrid mode (ffn_fused), the whole FFN runs behind the attention, two launches per block.
-static int denoise_chunk_row_resident(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st) {
+static int denoise_chunk_row_resident(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, const int32_t* d_t) {
   const int M = Bc * h->S, D = h->D, F = h->F, C = h->C;
   const bool pre_ffn2 = !h->ffn_fused;
   for (int i = 0; i < h->L; ++i) {
     const LayerW& w = h->layers[i];
     {
       const bool pre = pre_ffn2 && i > 0;
-      const LnGemmArgs a = lngemm_in_proj_args(h, ws, d_tokens, t, i, M, pre);
+      const LnGemmArgs a = lngemm_in_proj_args(h, ws, d_tokens, t, i, M, pre, d_t);
       ldm_handle::Scope sc(h, st, pre ? "gemm_ffn2_qkv_ln" : "gemm_qkv_ln", gemm_flops(M, 3 * D, D) + (pre ? gemm_flops(M, D, F) : 0.0),
                            (double)M * D * 8 + (double)M * 3 * D * 4 + (pre ? (double)M * F * 4 : 0.0));
       if (launch_lngemm16x3(a, st)) return h->fail(-4, "row-resident LayerNorm + GEMM: geometry not supported");
@@ -290,8 +297,13 @@ static int denoise_chunk_row_resident(ldm_handle* h, Workspace& ws, const int32_
 // ------------------------------------------------------------------------------------------ one pass
 // denoiser forward for `Bc` layouts whose tokens start at d_tokens -> ws.logits [Bc*S, Cp]   (skip_embed: the stack kernel's rows are
 // already in ws.P — the previous step's posterior wrote them)
-int ldm_host::denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed) {
+bool ldm_host::per_layout_t(const ldm_handle* h) { return !(h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6); }
+
+int ldm_host::denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed,
+                            const int32_t* d_t) {
+  if (d_t && !per_layout_t(h))   // the stack kernel's workgroups take ONE set of AdaLN rows per layer from its arguments
+    return h->fail(-4, "per-layout timesteps: precision fast_f16 on the stack kernel has no per-layout form (ldm_describe per_layout_t=0)");
   if (h->cfg.precision == LDM_PREC_FAST_F16)
-    return h->fused_attn == 6 ? denoise_chunk_stack(h, ws, d_tokens, t, Bc, st, skip_embed) : denoise_chunk_fast(h, ws, d_tokens, t, Bc, st);
-  return h->lngemm ? denoise_chunk_row_resident(h, ws, d_tokens, t, Bc, st) : denoise_chunk_tiled(h, ws, d_tokens, t, Bc, st);
+    return h->fused_attn == 6 ? denoise_chunk_stack(h, ws, d_tokens, t, Bc, st, skip_embed) : denoise_chunk_fast(h, ws, d_tokens, t, Bc, st, d_t);
+  return h->lngemm ? denoise_chunk_row_resident(h, ws, d_tokens, t, Bc, st, d_t) : denoise_chunk_tiled(h, ws, d_tokens, t, Bc, st, d_t);
 }

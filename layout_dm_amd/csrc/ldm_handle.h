@@ -252,6 +252,11 @@ struct ldm_handle {
   int32_t *tok_a = nullptr, *tok_b = nullptr;  // loop state ping-pong (max_batch)
   uint64_t* rng = nullptr;                      // device {seed, first_layout}
   int32_t* vb_err = nullptr;                    // error word of the scoring entry points (ldm_vb_api.cpp), allocated on first use
+  // per-layout timesteps (ldm_*_t): the call's host arrays staged on the device, max_batch entries each, allocated on first use
+  int32_t* st_t = nullptr;
+  uint64_t* st_layout = nullptr;
+  std::vector<int32_t> st_t_host;               // pageable copies the uploads read: the caller's arrays are done with at return
+  std::vector<uint64_t> st_layout_host;
   // profiling
   bool profiling = false;
   std::vector<ProfEntry> prof;
@@ -337,9 +342,15 @@ struct ldm_handle {
 namespace ldm_host {
 std::string& create_error();   // last ldm_create error of this thread (ldm_last_error(NULL))
 double gemm_flops(int M, int N, int K);
-int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false);
+// d_t: nullptr, or the chunk's Bc per-layout timesteps on the device (t is then not read); -4 where the engine has no per-layout form
+int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false,
+                  const int32_t* d_t = nullptr);
+bool per_layout_t(const ldm_handle* h);   // the handle's denoiser takes per-layout timesteps (ldm_describe per_layout_t)
+// h_t (B host timesteps, checked against [0, T)) -> the handle's staging buffer; *d_t = its device address (ldm_api.cpp)
+int stage_timesteps(ldm_handle* h, const int32_t* h_t, int B, hipStream_t st, const int32_t** d_t);
 // the arguments of the row-resident LayerNorm + GEMM launches on workspace `ws` (ldm_denoise.cpp; also ldm_dev.cpp ldm_dev_lngemm_run)
-ldm::LnGemmArgs lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre);
+ldm::LnGemmArgs lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, const int32_t* d_tokens, int t, int i, int M, bool pre,
+                                    const int32_t* d_t = nullptr);
 ldm::LnGemmArgs lngemm_linear1_args(const ldm_handle* h, const Workspace& ws, int i, int M);
 ldm::LnGemmArgs lngemm_head_args(const ldm_handle* h, const Workspace& ws, int M, bool pre);
 void fill_post(ldm_handle* h, ldm::PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off, int Bc);

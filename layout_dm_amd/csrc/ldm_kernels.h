@@ -60,6 +60,11 @@ struct LnArgs {
   float2* stats_out;      // [M] (mean, rstd) or nullptr   (deferred normalisation, fast mode)
   int M, D, S, ld16, ada;
   int raw;                // 1: y32 receives the UN-normalised x (embedding only), stats_out the statistics
+  // per-layout timesteps (ada, the ldm_*_t entry points): row m belongs to layout m / S and takes p0 = ada_tab + t_rows[m / S] *
+  // t_stride + layer_off, p1 = p0 + D (p0 / p1 above are ignored); t_rows == nullptr: p0 / p1 as given
+  const int32_t* t_rows;  // device [ceil(M / S)] timesteps, or nullptr
+  const float* ada_tab;   // the [T][L][2 D] AdaLN table
+  int t_stride, layer_off;   // floats: L * 2 D per timestep, layer * 2 D
 };
 void launch_layernorm(const LnArgs& a, hipStream_t st);
 
@@ -116,6 +121,11 @@ struct LnGemmArgs {
   // half either (tile loop: the LayerNorm output is rounded once; prologue: preAlo is not read).  With C16lo == nullptr (ReLU, panel_out) the
   // epilogue writes plain-fp16 hidden panels (LDM_PREC_HYBRID_F16: the FFN and the head in plain fp16, the attention path in the two-product form)
   int np_main, np_pre;
+  // per-layout timesteps (ada only; S must be set): the row's AdaLN parameters are ada_tab + t_rows[row / S] * t_stride + layer_off
+  // (scale) and + D (shift), read per lane at the normalisation step; t_rows == nullptr: p0 / p1, staged once per workgroup
+  const int32_t* t_rows;    // device [ceil(M / S)] timesteps, or nullptr
+  const float* ada_tab;     // the [T][L][2 D] AdaLN table
+  int t_stride, layer_off;  // floats
 };
 int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st);
 void lngemm_phase_read(unsigned long long* out8);   // (LDM_LNGEMM_TM=1: accumulated phase cycles, reset on read)
@@ -438,6 +448,8 @@ struct VbArgs {
   int ldl;
   const float* sched;      // device [8][n_attr][T+1] schedule buffers (ScheduleRow)
   int T, t;
+  const int32_t* t_rows;   // [B] per-layout timesteps in [0, T) (the ldm_*_t entry points), or nullptr: t for every layout
+  const uint64_t* layout_rows;   // [B] layout index of row b in the Philox key, added to first_layout (q_sample), or nullptr: b
   uint64_t seed, first_layout;   // Philox key / global index of layout 0 (q_sample)
   int f32_lse;             // 1: fp32 log-softmax and hardware exp / log (fast numerics mode)
   int B, S;

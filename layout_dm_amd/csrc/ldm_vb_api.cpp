@@ -1,5 +1,6 @@
 // Host side of scoring GIVEN layouts (include/ldm_hip.h: ldm_q_sample, ldm_vb_terms, ldm_vb_step): the forward noising draw,
-// the variational bound's terms of one timestep, and the two around one denoiser pass of the handle's own numerics mode.
+// the variational bound's terms of one timestep, and the two around one denoiser pass of the handle's own numerics mode — at ONE
+// timestep for the call, or (ldm_q_sample_t, ldm_vb_terms_t, ldm_vb_step_t) at a timestep per layout, one body for both.
 // Evaluation of a trained model only: no gradients, nothing of the handle's weights or schedule is written.
 // Tokens are checked by the kernels (ldm_vb_core.h token_error) into an error word the call reads back before it returns:
 // a refused call has synchronised the stream, like a successful one.
@@ -46,19 +47,50 @@ int check_t(ldm_handle* h, int t) {
   return 0;
 }
 
-}  // namespace
+// The timesteps of a call: ONE t (h_t == nullptr, the single-t entry points), or B per-layout values staged on the device
+// (the *_t entry points; h_layout: the layouts' indices in the Philox key, or nullptr: their row positions).
+struct CallT {
+  int t = 0;
+  const int32_t* d_t = nullptr;
+  const uint64_t* d_layout = nullptr;
+};
 
-extern "C" int ldm_q_sample(ldm_handle* h, const int32_t* d_x0, int t, uint64_t seed, uint64_t first_layout, int B,
-                            int32_t* d_xt, void* stream) {
+int begin_t(ldm_handle* h, int t, const int32_t* h_t, bool per_layout, const uint64_t* h_layout, int B, hipStream_t st, CallT& c) {
+  if (!per_layout) {
+    c.t = t;
+    return check_t(h, t);
+  }
+  if (int rc = stage_timesteps(h, h_t, B, st, &c.d_t)) return rc;
+  if (!h_layout) return 0;
+  if (!h->st_layout) {
+    if (int rc = h->dalloc(&h->st_layout, (size_t)h->cfg.max_batch)) return rc;
+    h->st_layout_host.resize((size_t)h->cfg.max_batch);
+  }
+  std::copy(h_layout, h_layout + B, h->st_layout_host.begin());   // (pageable: read by the time the upload returns, like stage_timesteps)
+  HIP_OK(h, hipMemcpyAsync(h->st_layout, h->st_layout_host.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  c.d_layout = h->st_layout;
+  return 0;
+}
+
+// rows [off, off + B) of the call
+void fill_vb(const ldm_handle* h, VbArgs& p, const CallT& c, int off, int B) {
+  fill_vb(h, p, c.t, B);
+  p.t_rows = c.d_t ? c.d_t + off : nullptr;
+  p.layout_rows = c.d_layout ? c.d_layout + off : nullptr;
+}
+
+int q_sample(ldm_handle* h, const int32_t* d_x0, int t, const int32_t* h_t, bool per_layout, const uint64_t* h_layout, uint64_t seed,
+             uint64_t first_layout, int B, int32_t* d_xt, void* stream) {
   int rc = check_ready(h, B);
   if (rc) return rc;
   if (!d_x0 || !d_xt) return h->fail(-1, "null argument");
-  if ((rc = check_t(h, t))) return rc;
   ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
+  CallT c;
+  if ((rc = begin_t(h, t, h_t, per_layout, h_layout, B, st, c))) return rc;
   if ((rc = err_begin(h, st))) return rc;
   VbArgs p{};
-  fill_vb(h, p, t, B);
+  fill_vb(h, p, c, 0, B);
   p.x0 = d_x0;
   p.xt_out = d_xt;
   p.seed = seed;
@@ -67,17 +99,18 @@ extern "C" int ldm_q_sample(ldm_handle* h, const int32_t* d_x0, int t, uint64_t 
   return err_end(h, st);
 }
 
-extern "C" int ldm_vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, int t, int B,
-                            double* d_sums, float* d_tok, void* stream) {
+int vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, int t, const int32_t* h_t, bool per_layout,
+             int B, double* d_sums, float* d_tok, void* stream) {
   int rc = check_ready(h, B);
   if (rc) return rc;
   if (!d_logits || !d_x0 || !d_xt || !d_sums) return h->fail(-1, "null argument");
-  if ((rc = check_t(h, t))) return rc;
   ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
+  CallT c;
+  if ((rc = begin_t(h, t, h_t, per_layout, nullptr, B, st, c))) return rc;
   if ((rc = err_begin(h, st))) return rc;
   VbArgs p{};
-  fill_vb(h, p, t, B);
+  fill_vb(h, p, c, 0, B);
   p.logits = d_logits;
   p.ldl = h->C;
   p.x0 = d_x0;
@@ -88,19 +121,20 @@ extern "C" int ldm_vb_terms(ldm_handle* h, const float* d_logits, const int32_t*
   return err_end(h, st);
 }
 
-extern "C" int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, uint64_t seed,
-                           uint64_t first_layout, int B, double* d_sums, void* stream) {
+int vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, const int32_t* h_t, bool per_layout, const uint64_t* h_layout,
+            uint64_t seed, uint64_t first_layout, int B, double* d_sums, void* stream) {
   int rc = check_ready(h, B);
   if (rc) return rc;
   if (!d_x0 || !d_sums) return h->fail(-1, "null argument");
-  if ((rc = check_t(h, t))) return rc;
   ON_DEVICE(h);
   hipStream_t st = (hipStream_t)stream;
+  CallT c;
+  if ((rc = begin_t(h, t, h_t, per_layout, h_layout, B, st, c))) return rc;
   if ((rc = err_begin(h, st))) return rc;
   {  // x_t ~ q(x_t | x_0) of the whole call — or the checked copy of a given x_t — into the handle's token buffer: the denoiser
      // embeds what it is handed, so a token outside the vocabulary must not reach it
     VbArgs q{};
-    fill_vb(h, q, t, B);
+    fill_vb(h, q, c, 0, B);
     q.x0 = d_x0;
     q.xt = d_xt;
     q.xt_out = h->tok_a;
@@ -113,9 +147,9 @@ extern "C" int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_
   for (int off = 0; off < B; off += h->chunk) {
     const int Bc = std::min(h->chunk, B - off);
     const size_t ro = (size_t)off * h->S;
-    if ((rc = denoise_chunk(h, ws, d_xt + ro, t, Bc, st))) return rc;
+    if ((rc = denoise_chunk(h, ws, d_xt + ro, c.t, Bc, st, false, c.d_t ? c.d_t + off : nullptr))) return rc;
     VbArgs p{};
-    fill_vb(h, p, t, Bc);
+    fill_vb(h, p, c, off, Bc);
     p.logits = ws.logits;
     p.ldl = h->Cp;
     p.x0 = d_x0 + ro;
@@ -124,4 +158,33 @@ extern "C" int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_
     launch_vb_terms(p, st);
   }
   return err_end(h, st);
+}
+
+}  // namespace
+
+extern "C" int ldm_q_sample(ldm_handle* h, const int32_t* d_x0, int t, uint64_t seed, uint64_t first_layout, int B,
+                            int32_t* d_xt, void* stream) {
+  return q_sample(h, d_x0, t, nullptr, false, nullptr, seed, first_layout, B, d_xt, stream);
+}
+extern "C" int ldm_q_sample_t(ldm_handle* h, const int32_t* d_x0, const int32_t* h_t, const uint64_t* h_layout, uint64_t seed,
+                              uint64_t first_layout, int B, int32_t* d_xt, void* stream) {
+  return q_sample(h, d_x0, 0, h_t, true, h_layout, seed, first_layout, B, d_xt, stream);
+}
+
+extern "C" int ldm_vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, int t, int B,
+                            double* d_sums, float* d_tok, void* stream) {
+  return vb_terms(h, d_logits, d_x0, d_xt, t, nullptr, false, B, d_sums, d_tok, stream);
+}
+extern "C" int ldm_vb_terms_t(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, int B,
+                              double* d_sums, float* d_tok, void* stream) {
+  return vb_terms(h, d_logits, d_x0, d_xt, 0, h_t, true, B, d_sums, d_tok, stream);
+}
+
+extern "C" int ldm_vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, uint64_t seed,
+                           uint64_t first_layout, int B, double* d_sums, void* stream) {
+  return vb_step(h, d_x0, d_xt, t, nullptr, false, nullptr, seed, first_layout, B, d_sums, stream);
+}
+extern "C" int ldm_vb_step_t(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, const uint64_t* h_layout,
+                             uint64_t seed, uint64_t first_layout, int B, double* d_sums, void* stream) {
+  return vb_step(h, d_x0, d_xt, 0, h_t, true, h_layout, seed, first_layout, B, d_sums, stream);
 }

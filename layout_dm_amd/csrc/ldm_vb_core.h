@@ -42,6 +42,14 @@ LDM_PT_HD int token_error(const TokenArgs& a, int x0, bool has_xt, int xt) {
   return e;
 }
 
+// Per-layout timesteps (ldm_*_t): layout b of a call is noised and scored at t_rows[b], and its Philox key carries the layout index
+// first_layout + layout_rows[b] — nullptr: the call's single t / the row position b, what the single-t entry points use.  One
+// layout may so stand in several rows of a call, at several t, and still draw what a single-t call at that t draws for it.
+LDM_PT_HD int row_t(const int32_t* t_rows, int t, int b) { return t_rows ? t_rows[b] : t; }
+LDM_PT_HD uint64_t row_layout(uint64_t first_layout, const uint64_t* layout_rows, int b) {
+  return first_layout + (layout_rows ? layout_rows[b] : (uint64_t)b);
+}
+
 // schedule entries of (attribute, t) the draw reads: log_cumprod_at / bt / ct and log_1_min_cumprod_ct at t
 struct NoiseSchedule {
   float LA, LB, LC, L1C;

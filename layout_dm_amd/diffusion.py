@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import itertools
 import logging
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -54,6 +54,28 @@ def batch_cuts(B: int, max_batch: int, round_: int) -> List[int]:
         return [B] if B > 0 else []
     step = (max_batch // round_) * round_ or max_batch
     return [step] * (B // step) + ([B % step] if B % step else [])
+
+
+class ElboCall(NamedTuple):
+    """One engine call of elbo(): rows start .. start + len(t) - 1 of draw `draw`'s (t, layout) pairs in t-major order."""
+    draw: int
+    start: int          # index of the call's first row among the draw's T * B pairs: pair i is (t = i // B, layout = i % B)
+    t: np.ndarray       # (n,) int32 timestep of every row
+    layout: np.ndarray  # (n,) int64 layout of every row
+
+
+def elbo_calls(B: int, T: int, n_draws: int, max_rows: int) -> List[ElboCall]:
+    """The engine calls elbo() makes on an engine with per-layout timesteps: the (draw, t, layout) triples flattened t-major
+    (layout fastest) and cut into calls of at most max_rows rows.  Rows of a call share a draw — the Philox seed is per call.
+    With B a multiple of max_rows every call is uniform in t (the cuts of the single-t path)."""
+    if B < 1 or T < 1 or n_draws < 1 or max_rows < 1:
+        raise ValueError("B, T, n_draws and max_rows must be >= 1")
+    calls = []
+    for d in range(n_draws):
+        for start in range(0, T * B, max_rows):
+            i = np.arange(start, min(start + max_rows, T * B), dtype=np.int64)
+            calls.append(ElboCall(d, start, (i // B).astype(np.int32), i % B))
+    return calls
 
 
 def timestep_schedule(num_timesteps: int, num_timesteps_eval: int, time_difference: float = 0.0):
@@ -496,8 +518,11 @@ class HipMaskAndReplaceDiffusion:
     def elbo(self, x0: torch.Tensor, n_draws: int = 1, seed: Optional[int] = None, first_layout: int = 0) -> torch.Tensor:
         """Per-layout variational bound on -log p(x_0) in nats per token, (B,) float64 on the device: the sum over t = 0 .. T - 1
         of the reference's kl_loss term (constrained.py:304-305: decoder_nll at t = 0, kl otherwise) at one drawn x_t per t,
-        averaged over n_draws independent draws (Philox keys seed, seed + 1, ...).  The whole batch goes through each t: T
-        denoiser passes per draw.  The reference's bound carries no prior term L_T = KL(q(x_T | x_0) || p(x_T)), so neither
+        averaged over n_draws independent draws (Philox keys seed, seed + 1, ...).  On an engine with per-layout timesteps
+        (Engine.per_layout_t) the T * B (t, layout) pairs of a draw are packed t-major into calls of up to max_batch rows
+        (elbo_calls): ceil(T * B / max_batch) denoiser passes per draw — 1 at B = 4, T = 100, max_batch = 512 — each row with the
+        bits its single-t call gives it; a call whose rows share one t (every call when B is a multiple of max_batch) is the
+        single-t call itself.  Elsewhere the whole batch goes through each t: T passes per draw.  The reference's bound carries no prior term L_T = KL(q(x_T | x_0) || p(x_T)), so neither
         does this one (L_T does not depend on the model: it shifts every checkpoint's bound alike).  A stochastic estimate: compare checkpoints or layouts under the same seed."""
         if n_draws < 1:
             raise ValueError("n_draws must be >= 1")
@@ -505,9 +530,22 @@ class HipMaskAndReplaceDiffusion:
         eng, T = self.engine, self.num_timesteps
         x0 = eng._tok(torch.as_tensor(x0))                       # staged once for all T passes
         sums = torch.empty((int(n_draws) * T, x0.shape[0], 4), dtype=torch.float64, device=eng.device)
-        for d in range(int(n_draws)):
-            for t in range(T):
-                self._vb_sums(x0, t, None, seed + d, first_layout, sums[d * T + t])
+        B = x0.shape[0]
+        if B and eng.per_layout_t:
+            # x0 tiled so that the rows of any call — layouts (start + k) % B, k = 0 .. n - 1 — are one contiguous slice of it
+            reps = -(-(B - 1 + min(eng.max_batch, T * B)) // B)
+            tiled = x0.repeat(reps, 1) if reps > 1 else x0
+            for c in elbo_calls(B, T, int(n_draws), eng.max_batch):
+                n, b0 = len(c.t), int(c.layout[0])
+                out = sums[c.draw * T:(c.draw + 1) * T].view(T * B, 4)[c.start:c.start + n]   # (t-major: the call's rows are contiguous)
+                if int(c.t[0]) == int(c.t[-1]):
+                    eng.vb_step(tiled[b0:b0 + n], int(c.t[0]), seed=seed + c.draw, first_layout=first_layout + b0, out=out)
+                else:
+                    eng.vb_step_t(tiled[b0:b0 + n], c.t, seed=seed + c.draw, first_layout=first_layout, layout=c.layout, out=out)
+        else:
+            for d in range(int(n_draws)):
+                for t in range(T):
+                    self._vb_sums(x0, t, None, seed + d, first_layout, sums[d * T + t])
         # one elementwise launch for the token means (the values vb_terms returns), then the T terms of a draw are added on
         # the host in their order, t = 0 first: B x T float64 additions, exactly the sum of the vb_terms calls
         mean = (sums / eng.S).cpu().numpy()
@@ -520,14 +558,19 @@ class HipMaskAndReplaceDiffusion:
 
     @torch.no_grad()
     def loss(self, x0: torch.Tensor, t: Optional[torch.Tensor] = None, pt: Optional[torch.Tensor] = None,
-             seed: Optional[int] = None, x_t: Optional[torch.Tensor] = None, first_layout: int = 0) -> Dict[str, torch.Tensor]:
+             seed: Optional[int] = None, x_t: Optional[torch.Tensor] = None, first_layout: int = 0,
+             grouped: bool = False) -> Dict[str, torch.Tensor]:
         """The reference's losses of one batch, {"kl_loss", "aux_loss"} (constrained.py:304-330 with adaptive_auxiliary_loss; no
         "aux_loss" when auxiliary_loss_weight is 0), as float64 scalars on the host.  t (B,) per-layout timesteps and pt their
         sampling probabilities: None -> sample_time() / time_weights()[t].  x_t: given states (B,S), else drawn per layout at
-        its own t (vb_terms' stream: a layout's draw depends on seed, its global index and its t alone).  Layouts are grouped
-        by t on the host, one denoiser pass per distinct value.  Cost: ldm_q_sample takes ONE t per call, so with drawn
-        x_t the whole batch is noised once per distinct t and the group picked out of it (a batch of 64 at ~45 distinct t:
-        45 small draw launches and 45 vb_step calls, each with its error-word read-back) — evaluation batches, not a hot path."""
+        its own t (vb_terms' stream: a layout's draw depends on seed, its global index and its t alone).
+        Cost: on an engine with per-layout timesteps (Engine.per_layout_t: every engine but `fast` on the reference's backbone)
+        the batch is ONE Engine.vb_step_t call per batch_cuts window — the draw, one denoiser pass per chunk with every layout
+        at its own t, the terms and one error-word read-back: a batch of 64 is one call whatever its t.  Elsewhere, and with
+        grouped=True (the earlier path, kept for comparison: same bits), layouts are grouped by t on the host, one denoiser
+        pass per distinct value; ldm_q_sample takes ONE t per call, so with drawn x_t the whole batch is noised once per
+        distinct t and the group picked out of it (a batch of 64 at ~45 distinct t: 45 small draw launches and 45 vb_step
+        calls, each with its error-word read-back)."""
         eng = self.engine
         x0 = eng._tok(torch.as_tensor(x0))
         B, T = x0.shape[0], self.num_timesteps
@@ -541,16 +584,24 @@ class HipMaskAndReplaceDiffusion:
         if x_t is not None:
             x_t = eng._tok(torch.as_tensor(x_t))
         seed = 0 if x_t is not None else self._draw_seed(seed)
-        sums = torch.empty((B, 4), dtype=torch.float64)
-        for tv in sorted(set(t.tolist())):
-            idx = (t == tv).nonzero().reshape(-1)
-            idx_d = idx.to(eng.device)
-            xt_all = x_t if x_t is not None else self.q_sample(x0, tv, seed, first_layout)
-            x0_g, xt_g = x0.index_select(0, idx_d), xt_all.index_select(0, idx_d)
-            part = torch.empty((idx.numel(), 4), dtype=torch.float64, device=eng.device)
-            for off, n in self._cut(idx.numel()):
-                eng.vb_step(x0_g[off:off + n], tv, xt=xt_g[off:off + n], out=part[off:off + n])
-            sums[idx] = part.cpu()
+        if not grouped and eng.per_layout_t:
+            part = torch.empty((B, 4), dtype=torch.float64, device=eng.device)
+            tn32 = t.numpy().astype(np.int32)
+            for off, n in self._cut(B):
+                eng.vb_step_t(x0[off:off + n], tn32[off:off + n], xt=None if x_t is None else x_t[off:off + n], seed=seed,
+                              first_layout=first_layout + off, out=part[off:off + n])
+            sums = part.cpu()
+        else:
+            sums = torch.empty((B, 4), dtype=torch.float64)
+            for tv in sorted(set(t.tolist())):
+                idx = (t == tv).nonzero().reshape(-1)
+                idx_d = idx.to(eng.device)
+                xt_all = x_t if x_t is not None else self.q_sample(x0, tv, seed, first_layout)
+                x0_g, xt_g = x0.index_select(0, idx_d), xt_all.index_select(0, idx_d)
+                part = torch.empty((idx.numel(), 4), dtype=torch.float64, device=eng.device)
+                for off, n in self._cut(idx.numel()):
+                    eng.vb_step(x0_g[off:off + n], tv, xt=xt_g[off:off + n], out=part[off:off + n])
+                sums[idx] = part.cpu()
         # B scalars from here on, on the host in float64
         mean = sums.numpy() / eng.S
         tn, ptn = t.numpy(), pt.double().numpy()
