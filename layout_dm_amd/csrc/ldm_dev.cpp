@@ -1,7 +1,8 @@
 // Development hooks of libldm_hip.so (NOT part of the public ABI in include/ldm_hip.h): the s_memtime phase sums of the instrumented
 // kernels (tools/phase_probe.py, lngemm_probe.py, attnout_probe.py) and a unit check of the fused attention + out_proj launch on
 // synthetic operands (tests/test_attnout_gpu.py), and one row-resident LayerNorm + GEMM launch of a live handle on the caller's rows
-// (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py), and one launch of a LayerNorm / GEMM / attention kernel of the tiled engines on the caller's
+// (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py), and one fused attention + out_proj (+ FFN) launch of a live handle on the caller's panels
+// (ldm_dev_attnout_run, tests/test_attnout_kernel_gpu.py), and one launch of a LayerNorm / GEMM / attention kernel of the tiled engines on the caller's
 // buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py).  Nothing in the product path calls
 // into this file.
 #include <hip/hip_runtime.h>
@@ -234,6 +235,53 @@ extern "C" int ldm_dev_lngemm_run(ldm_handle* h, const ldm_dev_lngemm_io* io) {
   const bool rows_missing = !a.tokens && !pre && !a.x;
   if (rows_missing || (a.ada && !a.y32) || (!a.C32 && !a.C16)) return h->fail(-1, "ldm_dev_lngemm_run: null operand");
   if (launch_lngemm16x3(a, 0)) return h->fail(-1, "row-resident LayerNorm + GEMM: geometry not supported");
+  HIP_OK(h, hipStreamSynchronize(0));
+  HIP_OK(h, hipGetLastError());
+  return 0;
+}
+
+// ONE attnout16x3_k launch (kernels_attnout.hip: attention + out_proj, in the hybrid mode + LayerNorm-2 + the plain-fp16 FFN) of a live handle
+// on the caller's device buffers: the arguments are the product's own for `layer` (ldm_denoise.cpp denoise_chunk_row_resident: out_proj's
+// k-step image, bias and pre-scale, the two-product flag, the FFN's chunk image and parameters, 1 / sqrt(dh)) with the panels, their stride,
+// res, out / ffn_out, B and S swapped for the caller's — S as well: no weight depends on it and the launch takes any 1 <= S <= 128.  The io
+// struct carries the capacity of every buffer; no reference arithmetic here (tests/_attnout_cases.py holds the float64 side).  -1, before any
+// launch, for a handle without the kernel and for whatever the kernel's stated preconditions forbid; -2 on a HIP error.
+struct ldm_dev_attnout_io {
+  int32_t layer, B, S, pad_;
+  const void *qkv_hi, *qkv_lo;   // [48 panels] of panel_stride bytes: 64 bytes per row
+  uint64_t panel_stride;         // bytes between panels
+  const float* res;              // [B S, 464] residual rows
+  float* out;                    // [B S, 464]: `out` of the plain forms, `ffn_out` of the FFN form (which may alias res: the product's own use)
+  int64_t panel_rows;            // capacities: rows (of 64 bytes) behind the start of EVERY panel, the last one included
+  int64_t res_rows, out_rows;    // ... rows of 464 floats
+};
+extern "C" int ldm_dev_attnout_run(ldm_handle* h, const ldm_dev_attnout_io* io) {
+  if (!h || !io) return -1;
+  if (!h->finalized) return h->fail(-1, "weights not finalized");
+  if (!h->attnout) return h->fail(-1, "the handle has no fused attention + out_proj kernel");
+  if (io->layer < 0 || io->layer >= h->L) return h->fail(-1, "ldm_dev_attnout_run: layer out of range");
+  const int64_t B = io->B, S = io->S;
+  if (B < 1 || S < 1 || S > 128 || B * S > INT32_MAX) return h->fail(-1, "ldm_dev_attnout_run: B < 1, S outside [1, 128] or B S beyond int");
+  auto ok16 = [](const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (!ok16(io->qkv_hi) || !ok16(io->qkv_lo) || !ok16(io->res) || !ok16(io->out))
+    return h->fail(-1, "ldm_dev_attnout_run: null or misaligned pointer");
+  // every layout reads 128 rows from its first one in every panel (launch_attnout16x3 states the same bound on the stride)
+  const uint64_t reach = (uint64_t)((B - 1) * S + 128);
+  if ((io->panel_stride & 15) || io->panel_stride < reach * 64) return h->fail(-1, "ldm_dev_attnout_run: panel_stride");
+  if (io->panel_rows < (int64_t)reach) return h->fail(-1, "ldm_dev_attnout_run: panels shorter than the launch's 128-row reach");
+  if (io->res_rows < B * S || io->out_rows < B * S) return h->fail(-1, "ldm_dev_attnout_run: res / out shorter than B S rows");
+  ON_DEVICE(h);
+  const LayerW& w = h->layers[io->layer];
+  AttnOutArgs a{};
+  a.qkv_hi = static_cast<const char*>(io->qkv_hi); a.qkv_lo = static_cast<const char*>(io->qkv_lo); a.panel_stride = (size_t)io->panel_stride;
+  a.w_img = (const char*)w.x3_out_kstep;
+  a.res = io->res; a.bias = w.b_out; a.out = io->out;
+  a.S = (int)S; a.D = h->D; a.scale = 1.0f / sqrtf((float)h->dh); a.out_scale = w.s_out; a.w2 = h->w2p;
+  if (h->ffn_fused) {
+    a.ffn_img = (const char*)w.ffn16_img; a.ffn_gamma = w.g2; a.ffn_beta = w.be2; a.ffn_b1 = w.b1; a.ffn_b2 = w.b2;
+    a.ffn_out = io->out; a.F = h->F; a.n_chunks = h->F / 32;
+  }
+  if (launch_attnout16x3(a, (int)B, 0)) return h->fail(-1, "fused attention + out_proj: geometry not supported");
   HIP_OK(h, hipStreamSynchronize(0));
   HIP_OK(h, hipGetLastError());
   return 0;
