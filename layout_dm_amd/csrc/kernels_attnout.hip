@@ -758,8 +758,6 @@ void attnout_phase_read(unsigned long long* out24) {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_attnout_phase), z, sizeof(z));
 }
 
-bool attnout16x3_supported(int S, int H, int dh, int D) { return S >= 1 && S <= 128 && H == 8 && dh == 58 && D == 464; }
-
 int launch_attnout16x3(const AttnOutArgs& a, int B, hipStream_t st) {
   if (!attnout16x3_supported(a.S, 8, 58, a.D) || B < 1 || (a.panel_stride & 15) || !a.qkv_hi || !a.qkv_lo || !a.w_img) return -1;
   // every layout reads 128 rows of 64 bytes from its first row, in every panel: the last one ends 128 - S rows behind the B * S rows in use

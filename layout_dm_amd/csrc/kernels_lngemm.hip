@@ -842,7 +842,7 @@ void lngemm_phase_read(unsigned long long* out8) {
 
 int launch_lngemm16x3(const LnGemmArgs& a, hipStream_t st) {
   // (everything LnGemmArgs documents or the kernel assumes is checked here, not only by ldm_create)
-  if (a.D != 464 || a.n_tiles < 2 || (a.n_tiles & 1) || a.n_tiles * 32 > 2048 || a.N > a.n_tiles * 32 || (a.N & 3) || a.M < 1) return -1;
+  if (!lngemm16x3_supported(a.D, a.N, a.n_tiles) || a.M < 1) return -1;
   if (a.tokens && a.S <= 0) return -1;
   // three output forms: fp32 (no ReLU) | ReLU + hi / lo fp16 rows | hi / lo fp16 panels without ReLU (q / k / v for kernels_attnout.hip);
   // the epilogue addresses with 32-bit byte offsets

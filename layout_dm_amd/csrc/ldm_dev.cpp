@@ -207,13 +207,13 @@ struct ldm_dev_lngemm_io {
 extern "C" int ldm_dev_lngemm_run(ldm_handle* h, const ldm_dev_lngemm_io* io) {
   if (!h || !io) return -1;
   if (!h->finalized) return h->fail(-1, "weights not finalized");
-  if (!h->lngemm) return h->fail(-1, "the handle has no row-resident LayerNorm + GEMM kernels");
+  if (h->plan.structure != Structure::RowResident) return h->fail(-1, "the handle has no row-resident LayerNorm + GEMM kernels");
   if (io->M < 1 || io->launch < 0 || io->launch > 2) return h->fail(-1, "ldm_dev_lngemm_run: bad launch / M");
   const bool in_proj = io->launch == 0, lin1 = io->launch == 1, pre = io->prologue != 0;
   if (in_proj && (io->layer < 0 || io->layer >= h->L || io->t < 0 || io->t >= h->T)) return h->fail(-1, "ldm_dev_lngemm_run: layer / timestep out of range");
   if (lin1 && (io->layer < 0 || io->layer >= h->L)) return h->fail(-1, "ldm_dev_lngemm_run: layer out of range");
   // the forms the handle's own pass runs: no linear1 / linear2 launches behind the fused FFN, linear2 in front of in_proj from layer 1 on
-  if ((lin1 || pre) && h->ffn_fused) return h->fail(-1, "ldm_dev_lngemm_run: the handle's FFN runs behind the attention");
+  if ((lin1 || pre) && h->plan.ffn_fused) return h->fail(-1, "ldm_dev_lngemm_run: the handle's FFN runs behind the attention");
   if (pre && (lin1 || (in_proj && io->layer < 1))) return h->fail(-1, "ldm_dev_lngemm_run: no prologue in front of this launch");
   ON_DEVICE(h);
   Workspace ws{};   // the launch's view of the caller's buffers, under the names the product's pass gives them
@@ -241,7 +241,7 @@ extern "C" int ldm_dev_lngemm_run(ldm_handle* h, const ldm_dev_lngemm_io* io) {
 }
 
 // ONE attnout16x3_k launch (kernels_attnout.hip: attention + out_proj, in the hybrid mode + LayerNorm-2 + the plain-fp16 FFN) of a live handle
-// on the caller's device buffers: the arguments are the product's own for `layer` (ldm_denoise.cpp denoise_chunk_row_resident: out_proj's
+// on the caller's device buffers: the arguments are the product's own for `layer` (ldm_denoise.cpp attnout_args: out_proj's
 // k-step image, bias and pre-scale, the two-product flag, the FFN's chunk image and parameters, 1 / sqrt(dh)) with the panels, their stride,
 // res, out / ffn_out, B and S swapped for the caller's — S as well: no weight depends on it and the launch takes any 1 <= S <= 128.  The io
 // struct carries the capacity of every buffer; no reference arithmetic here (tests/_attnout_cases.py holds the float64 side).  -1, before any
@@ -258,7 +258,7 @@ struct ldm_dev_attnout_io {
 extern "C" int ldm_dev_attnout_run(ldm_handle* h, const ldm_dev_attnout_io* io) {
   if (!h || !io) return -1;
   if (!h->finalized) return h->fail(-1, "weights not finalized");
-  if (!h->attnout) return h->fail(-1, "the handle has no fused attention + out_proj kernel");
+  if (!h->plan.attnout) return h->fail(-1, "the handle has no fused attention + out_proj kernel");
   if (io->layer < 0 || io->layer >= h->L) return h->fail(-1, "ldm_dev_attnout_run: layer out of range");
   const int64_t B = io->B, S = io->S;
   if (B < 1 || S < 1 || S > 128 || B * S > INT32_MAX) return h->fail(-1, "ldm_dev_attnout_run: B < 1, S outside [1, 128] or B S beyond int");
@@ -271,16 +271,12 @@ extern "C" int ldm_dev_attnout_run(ldm_handle* h, const ldm_dev_attnout_io* io) 
   if (io->panel_rows < (int64_t)reach) return h->fail(-1, "ldm_dev_attnout_run: panels shorter than the launch's 128-row reach");
   if (io->res_rows < B * S || io->out_rows < B * S) return h->fail(-1, "ldm_dev_attnout_run: res / out shorter than B S rows");
   ON_DEVICE(h);
-  const LayerW& w = h->layers[io->layer];
-  AttnOutArgs a{};
-  a.qkv_hi = static_cast<const char*>(io->qkv_hi); a.qkv_lo = static_cast<const char*>(io->qkv_lo); a.panel_stride = (size_t)io->panel_stride;
-  a.w_img = (const char*)w.x3_out_kstep;
-  a.res = io->res; a.bias = w.b_out; a.out = io->out;
-  a.S = (int)S; a.D = h->D; a.scale = 1.0f / sqrtf((float)h->dh); a.out_scale = w.s_out; a.w2 = h->w2p;
-  if (h->ffn_fused) {
-    a.ffn_img = (const char*)w.ffn16_img; a.ffn_gamma = w.g2; a.ffn_beta = w.be2; a.ffn_b1 = w.b1; a.ffn_b2 = w.b2;
-    a.ffn_out = io->out; a.F = h->F; a.n_chunks = h->F / 32;
-  }
+  Workspace ws{};   // the launch's view of the caller's buffers, under the names the product's pass gives them
+  ws.qkvp_hi = static_cast<__half*>(const_cast<void*>(io->qkv_hi)); ws.qkvp_lo = static_cast<__half*>(const_cast<void*>(io->qkv_lo));
+  ws.P = const_cast<float*>(io->res); ws.Q = io->out;
+  AttnOutArgs a = ldm_host::attnout_args(h, ws, io->layer);
+  a.panel_stride = (size_t)io->panel_stride; a.S = (int)S;
+  if (a.ffn_img) a.ffn_out = io->out;   // (the product writes x + attention + FFN over res; here to the caller's `out`, which may alias it)
   if (launch_attnout16x3(a, (int)B, 0)) return h->fail(-1, "fused attention + out_proj: geometry not supported");
   HIP_OK(h, hipStreamSynchronize(0));
   HIP_OK(h, hipGetLastError());

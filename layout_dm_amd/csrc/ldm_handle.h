@@ -1,5 +1,6 @@
 // Host side of libldm_hip.so, shared declarations: the handle (packed weights, per-lane activation workspaces, staging
 // buffers, hipGraph cache, profiling) and the helpers the translation units of the C-ABI share.
+//   ldm_engine_plan.h  which engine a configuration runs, its geometry and buffer sizes — or why it is refused (host-pure; ldm_handle::plan)
 //   ldm_api.cpp      lifecycle, parity hooks, result packaging, near-tie report, introspection
 //   ldm_weights.cpp  checkpoint upload, fp16 / LDS weight images, parameter tables (ldm_load_weight / ldm_finalize_weights)
 //   ldm_denoise.cpp  the launch sequence of one denoiser pass over a chunk, per numerics mode
@@ -125,11 +126,8 @@ struct GraphEntry {
   }
 };
 
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-
-// The activations of ONE chunk of layouts on their way through the denoiser.  A mode allocates the members its launches use
-// (ldm_create) and leaves the others nullptr.
+// The activations of ONE chunk of layouts on their way through the denoiser.  ldm_create allocates the members the plan counts
+// (ldm_engine_plan.h WorkspaceCounts, member for member) and leaves the others nullptr.
 struct Workspace {
   float *P = nullptr, *Q = nullptr;   // residual stream, ping-pong [rows, D]
   float* logits = nullptr;            // [chunk * S, Cp]
@@ -142,11 +140,11 @@ struct Workspace {
 };
 
 struct ldm_handle {
-  ldm_config cfg{};
+  ldm_config cfg{};    // as the caller gave it
+  EnginePlan plan;     // what this handle runs: engine structure and options, derived geometry, chunk / lanes (ldm_engine_plan.h)
   int device = 0;
   std::string err;
-  // geometry
-  int S = 0, C = 0, D = 0, F = 0, H = 0, dh = 0, L = 0, T = 0, Dp = 0, Fp = 0, Cp = 0, chunk = 0;
+  int D = 0, F = 0, H = 0, L = 0, T = 0;   // cfg's d_model, d_ff, n_head, n_layer, n_step
   VocabTables vocab{};
   // weights
   std::map<std::string, Raw> raw;
@@ -156,36 +154,13 @@ struct ldm_handle {
   const float *emb = nullptr, *head_g = nullptr, *head_b = nullptr, *head_w = nullptr;
   __half *head_w16 = nullptr, *head_w16lo = nullptr;
   float head_s = 1.f;
-  // split mode on the reference's backbone: the three LayerNorm-fed GEMMs (AdaLN + in_proj, norm2 + linear1, head LN + head)
-  // run as ONE row-resident launch each (kernels_lngemm.hip) instead of a LayerNorm launch + gemm16x3_k, and linear2 as the GEMM
-  // prologue of the next of them (the next layer's in_proj, or the head) — unless the hybrid mode's FFN is fused (ffn_fused)
-  bool lngemm = false;
-  void* x3_head = nullptr;
-  int x3_qkv_tiles = 0, x3_ffn1_tiles = 0, x3_head_tiles = 0;
-  // r06: attention and out_proj of the split mode as ONE layout-resident launch (kernels_attnout.hip); q / k / v travel from in_proj
-  // to it as head-padded hi / lo fp16 PANELS (qkvp_hi / qkvp_lo: [48][panel_rows][32]); LDM_DEV=1 LDM_X3_ATTNOUT=0: attn16x3_k + gemm16x3_k
-  bool attnout = false;
-  size_t panel_rows = 0;
-  // r06: the hidden activations (linear1 -> ReLU -> linear2) travel panel-major as well between linear1 and the linear2 GEMM prologue:
-  // full-line stores in linear1's epilogue, 2-KiB-contiguous A loads in the prologue; LDM_DEV=1 LDM_X3_HIDPANEL=0: row-major
-  bool hid_panels = false;
-  // two-product form of the split mode's WEIGHT GEMMs: activations hi + lo, weights fp16 only (kernels_lngemm.hip / kernels_attnout.hip W2)
-  bool w2p = false;
-  // created as LDM_PREC_MIXED_F16 (1) / LDM_PREC_HYBRID_F16 (2): cfg.precision then reads LDM_PREC_SPLIT_F16 — every other choice is the split mode's
-  int mixed = 0;
-  // products per k16-step (kernels_lngemm.hip NPM / NPP): of the attention path's GEMMs (in_proj; out_proj: w2p) and of linear1 / linear2 / the head.
-  // split 3 / 3, mixed 2 / 2, hybrid 2 / 1 (the FFN and the head in plain fp16: LayerNorm output, hidden activations and weights rounded once)
-  int np_w = 3, np_ffn = 3;
-  // hybrid: linear1 + ReLU + linear2 + residual in plain fp16 behind the attention, in the SAME launch (kernels_attnout.hip FFN): two launches
-  // per block instead of linear1 -> plain-fp16 panels -> linear2 as the GEMM prologue of the next launch; LDM_DEV=1 LDM_HYB_FFN=0: that form
-  bool ffn_fused = false;
-  bool balanced_chunks = true;   // ldm_loop.cpp run_loop_body: a call's passes share its layouts evenly; LDM_DEV=1 LDM_BALANCED_CHUNKS=0: full chunks + a remainder
+  void* x3_head = nullptr;   // RowResident: hi | lo tile image of the vocabulary head (kernels_lngemm.hip)
   std::vector<void*> owned;    // everything hipMalloc'ed by the handle for its lifetime
   std::vector<void*> derived;  // what ldm_finalize_weights derives from the checkpoint (fp16 / split copies, LDS images, parameter
                                // tables): freed and rebuilt when the weights are finalized again (a reload used to leak them)
   bool to_derived = false;     // dalloc's destination while ldm_finalize_weights runs
   int n_cu = 256;              // compute units of the device: the batch quantum of the one-launch loop (one workgroup per layout)
-  // Lanes: chunks c, c + n_lanes, ... form lane (c % n_lanes); every lane has its own workspace (ws[lane]: what its launches
+  // Lanes (plan.n_lanes, plan.lane_offset_us): chunks c, c + n_lanes, ... form lane (c % n_lanes); every lane has its own workspace (ws[lane]: what its launches
   // and its captured graph are given), stream and captured graph, and the lanes run CONCURRENTLY, lane l starting
   // l * lane_offset_us late.  Why: the fused kernels alternate HBM-bound phases (row loads / stores, ~30 % of a block) with
   // MFMA-bound phases, and with one kernel on the whole chip every CU hits the memory phase at the same moment (all-CU burst
@@ -195,9 +170,7 @@ struct ldm_handle {
   std::vector<hipStream_t> lane_stream;
   std::vector<hipEvent_t> lane_done;
   hipEvent_t fork_ev = nullptr;
-  int n_lanes = 1, lane_offset_us = 0;
-  // fast-mode (fp16 LDS-DMA GEMM + MFMA attention) layout: K padded to 64, heads padded 58 -> 64
-  int Dq = 0, HD = 0, Fq = 0;
+  // fast-mode (fp16 LDS-DMA GEMM + MFMA attention) layout: K padded to 64, heads padded 58 -> 64 (plan.Dq / HD / Fq)
   struct FastLayer {
     __half *w_in = nullptr, *w_out = nullptr, *w1 = nullptr, *w2 = nullptr;  // head-padded fp16 copies (generic tiled GEMMs)
     void* attn_head_img_ks = nullptr;  // per head: 6 in_proj tiles (k-slot K) + its 2 out-proj slabs (stack kernel)
@@ -208,28 +181,18 @@ struct ldm_handle {
   std::vector<FastLayer> fast;
   __half* fast_head = nullptr;
   void* head_img_ks = nullptr;  // vocabulary head as 32-class tile images, K axis in k-slot order (stack kernel)
-  int fused_attn = 6;  // 6: the layout-resident stack kernel (kernels_stack.hip: all layers + vocabulary head per launch, rows
-                       //    in the out-projection accumulators; the reference's backbone on both of its datasets);
-                       // 0: generic tiled kernels (LayerNorm -> gemm16 -> attention16 -> ...) for every other accepted
-                       //    geometry (and as an A/B / cross-check of the stack kernel: LDM_FUSED_ATTN=0)
   // parameter-table LDS images of the loop kernel (ldm_kernels.h StackTables), built by build_loop_tables
   float *tbl_att_static = nullptr, *tbl_att_dyn = nullptr, *tbl_ffn = nullptr, *tbl_head = nullptr;
-  int rel_loop = 1;    // cond=relation inside the one-launch loop (LDM_REL_LOOP=0: the per-step path)
-  int stack_loop = 1;  // the WHOLE reverse loop of a layout in its workgroup (kernels_stack.hip HEAD == 2): one launch per
-                       // sampling call, the step's tail behind the vocabulary head (LDM_STACK_LOOP=0: one stack launch +
-                       // one posterior launch per step, captured in per-lane hipGraphs — the r02 path)
   // Step-0 logits cache of the one-launch loop (ldm_loop.cpp run_loop_fused, kernels_stack.hip): an unconditional call starts
   // from all-[MASK] layouts, whose first denoiser pass depends on the checkpoint, the first timestep and S alone.  The first
   // ldm_sample_loop call with a new (t_model[0], S) runs that pass once for ONE layout (same kernel, writing the head's tiles
   // in register order) on the caller's stream in front of the real launch; from then on every all-[MASK] layout reads the table.
-  // At most kStep0Slots keys, the oldest replaced; every (re)load of a weight drops all of them (LDM_DEV=1 LDM_STEP0_CACHE=0: off).
+  // At most kStep0Slots keys, the oldest replaced; every (re)load of a weight drops all of them (plan.step0_cache).
   struct Step0Entry {
     int t = -1, S = 0, slot = 0;
     hipStream_t built_on = nullptr;   // the build is ordered in front of later work of this stream ...
     bool settled = false;             // ... and, once its event has been seen complete, of every stream
   };
-  static constexpr int kStep0Slots = 4;
-  int step0_cache = 1;
   float* step0_tab = nullptr;        // [kStep0Slots][kStackStep0Floats]
   int32_t* step0_tok = nullptr;      // an all-[MASK] row [S] | the build launch's token output [S]
   uint8_t* step0_flags = nullptr;    // [max_batch]: 1 = the layout of the last ldm_sample_loop call took the shortcut
@@ -345,7 +308,6 @@ double gemm_flops(int M, int N, int K);
 // d_t: nullptr, or the chunk's Bc per-layout timesteps on the device (t is then not read); -4 where the engine has no per-layout form
 int denoise_chunk(ldm_handle* h, Workspace& ws, const int32_t* d_tokens, int t, int Bc, hipStream_t st, bool skip_embed = false,
                   const int32_t* d_t = nullptr);
-bool per_layout_t(const ldm_handle* h);   // the handle's denoiser takes per-layout timesteps (ldm_describe per_layout_t)
 // h_t (B host timesteps, checked against [0, T)) -> the handle's staging buffer; *d_t = its device address (ldm_api.cpp)
 int stage_timesteps(ldm_handle* h, const int32_t* h_t, int B, hipStream_t st, const int32_t** d_t);
 // the arguments of the row-resident LayerNorm + GEMM launches on workspace `ws` (ldm_denoise.cpp; also ldm_dev.cpp ldm_dev_lngemm_run)
@@ -353,6 +315,16 @@ ldm::LnGemmArgs lngemm_in_proj_args(const ldm_handle* h, const Workspace& ws, co
                                     const int32_t* d_t = nullptr);
 ldm::LnGemmArgs lngemm_linear1_args(const ldm_handle* h, const Workspace& ws, int i, int M);
 ldm::LnGemmArgs lngemm_head_args(const ldm_handle* h, const Workspace& ws, int M, bool pre);
+// ... and of the fused attention + out_proj (+ FFN) launch of layer i over Bc layouts (also ldm_dev.cpp ldm_dev_attnout_run)
+ldm::AttnOutArgs attnout_args(const ldm_handle* h, const Workspace& ws, int i);
+// the stack kernel's view of the loaded weights: per-layer images and parameters (AdaLN rows of timestep t, or nullptr: the loop kernel
+// reads its tables), the vocabulary head writing to `logits` (or nullptr), the loop kernel's parameter tables
+struct StackWeights {
+  ldm::FusedLayerSet ls;
+  ldm::StackHead head;
+  ldm::StackTables tables;
+};
+StackWeights stack_weights(const ldm_handle* h, int t, float* logits);
 void fill_post(ldm_handle* h, ldm::PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off, int Bc);
 int check_ready(ldm_handle* h, int B);
 int check_sampler(ldm_handle* h, const ldm_sampler* s);

@@ -10,6 +10,7 @@
 #include <set>
 #include <utility>
 
+#include "ldm_engine_plan.h"
 #include "ldm_knobs.h"
 
 namespace ldm {
@@ -193,9 +194,7 @@ struct StackLoop {
   float* logits0_out;
   uint8_t* step0_flags;
 };
-constexpr int kStackStep0Floats = 5 * 16 * 256;
-// largest sub-vocabulary (body + [PAD] + [MASK]) the fused tail takes: 3 class slots on each of a group's 16 lanes
-constexpr int kStackPostMaxLive = 48;
+// (kStackStep0Floats and kStackPostMaxLive: ldm_engine_plan.h, which sizes the handle's buffers from them)
 constexpr int kStackLoopMaxSteps = 128;  // timesteps travel in the kernel arguments
 void launch_stack_loop(const FusedLayerSet& ls, int F, int N, int B, int S, int H, int dh, const StackHead& head,
                        const StackLoop& lp, hipStream_t st);
@@ -389,7 +388,6 @@ struct AttnOutArgs {
   float* ffn_out;
   int F, n_chunks;
 };
-bool attnout16x3_supported(int S, int H, int dh, int D);
 int launch_attnout16x3(const AttnOutArgs& a, int B, hipStream_t st);   // -1: geometry not supported
 void attnout_phase_read(unsigned long long* out24);   // (LDM_ATTNOUT_TM=1: accumulated phase cycles, reset on read)
 
@@ -436,6 +434,7 @@ struct PostArgs {
   float tie_rel, tie_abs;
 };
 enum ScheduleRow { kLogAt = 0, kLogBt, kLogCt, kLogCumAt, kLogCumBt, kLogCumCt, kLog1mCt, kLog1mCumCt, kNumSched };
+static_assert(kNumSched == kSchedRows, "ldm_engine_plan.h sizes the schedule buffer");
 void launch_posterior_sample(const PostArgs& p, hipStream_t st);
 void launch_set_rng(uint64_t* rng, uint64_t seed, uint64_t first_layout, hipStream_t st);
 

@@ -7,17 +7,17 @@ using namespace ldm_host;
 void ldm_host::fill_post(ldm_handle* h, PostArgs& p, const ldm_cond* cond, const ldm_sampler* s, size_t layout_off,
                       int Bc) {
   p.sched = h->sched;
-  p.f32_lse = h->cfg.precision == LDM_PREC_FAST_F16 ? 1 : 0;
+  p.f32_lse = h->plan.fast() ? 1 : 0;
   p.T = h->T;
   p.B = Bc;
-  p.S = h->S;
+  p.S = h->plan.S;
   p.v = h->vocab;
   p.rng = h->rng;
   if (cond) {
-    const size_t ro = layout_off * h->S;
+    const size_t ro = layout_off * h->plan.S;
     p.cond_seq = cond->d_cond_seq ? cond->d_cond_seq + ro : nullptr;
     p.strong = cond->d_strong_mask ? cond->d_strong_mask + ro : nullptr;
-    p.weak = cond->d_weak_logits ? cond->d_weak_logits + layout_off * h->C * h->S : nullptr;
+    p.weak = cond->d_weak_logits ? cond->d_weak_logits + layout_off * h->plan.C * h->plan.S : nullptr;
     p.pad_disable = cond->pad_disable;
   }
   if (s) {
@@ -40,7 +40,7 @@ int ldm_host::check_sampler(ldm_handle* h, const ldm_sampler* s) {
   if (s->kind < 0 || s->kind > 4) return h->fail(-1, "unknown sampler kind %d", s->kind);
   if (s->kind != LDM_SAMPLE_DETERMINISTIC && !(s->temperature > 0.f)) return h->fail(-1, "temperature must be > 0");
   if (s->kind == LDM_SAMPLE_TOP_P && !(s->top_p > 0.f && s->top_p <= 1.f)) return h->fail(-1, "top_p must be in (0,1]");
-  if (s->kind == LDM_SAMPLE_TOP_K && (s->top_k < 1 || s->top_k > h->C)) return h->fail(-1, "top_k out of range");
+  if (s->kind == LDM_SAMPLE_TOP_K && (s->top_k < 1 || s->top_k > h->plan.C)) return h->fail(-1, "top_k out of range");
   return 0;
 }
 
@@ -53,12 +53,12 @@ int ldm_host::check_sampler(ldm_handle* h, const ldm_sampler* s) {
 int ldm_host::check_live_temperature(ldm_handle* h, const ldm_sampler* s) {
   if (s->kind == LDM_SAMPLE_DETERMINISTIC) return 0;
   const double log_eps = std::log(1e-30);  // util.py:8
-  const double dead_mass = (double)h->C * std::exp(log_eps / (double)s->temperature);
+  const double dead_mass = (double)h->plan.C * std::exp(log_eps / (double)s->temperature);
   if (dead_mass > std::ldexp(1.0, -24))
     return h->fail(-1, "temperature %g puts %.3g of the mass on classes outside a token's sub-vocabulary (more than 2^-24): "
                        "the step / loop draw on the live classes only and must be given temperature <= %.4f for %d classes",
                    (double)s->temperature, dead_mass,
-                   -log_eps / std::log(std::ldexp(1.0, 24) * (double)h->C), h->C);
+                   -log_eps / std::log(std::ldexp(1.0, 24) * (double)h->plan.C), h->plan.C);
   return 0;
 }
 
@@ -76,10 +76,10 @@ static int check_relation(ldm_handle* h, const ldm_relation* rel, const ldm_cond
   PostArgs probe{};
   fill_post(h, probe, nullptr, nullptr, 0, 1);
   const bool three_launch = !loop_fusable(h, rel) && !relation_step_supported(probe);
-  for (int l = 0; three_launch && l < h->n_lanes; ++l) {
+  for (int l = 0; three_launch && l < h->plan.n_lanes; ++l) {
     if (h->ws[l].rel_logp) continue;
     float* buf = nullptr;
-    int rc = h->dalloc(&buf, (size_t)h->chunk * h->C * h->S, false);
+    int rc = h->dalloc(&buf, (size_t)h->plan.chunk * h->plan.C * h->plan.S, false);
     if (rc) return rc;
     h->ws[l].rel_logp = buf;
   }
@@ -92,7 +92,7 @@ void ldm_host::fill_rel(ldm_handle* h, RelArgs& a, const ldm_relation* rel, size
   a.centres = rel->d_centres;
   for (int x = 0; x < 4; ++x) a.canvas_bins[x] = rel->canvas_bins[x];
   a.step = rel->relation_lambda / (14.0f * (float)rel->n_graph_total);
-  a.num_update = rel->num_update; a.B = Bc; a.C = h->C; a.S = h->S; a.A = h->cfg.n_attr;
+  a.num_update = rel->num_update; a.B = Bc; a.C = h->plan.C; a.S = h->plan.S; a.A = h->cfg.n_attr;
   a.n_category = h->cfg.n_category; a.n_bin = h->cfg.n_bin; a.pad_id = h->vocab.pad_id;
 }
 
@@ -105,33 +105,35 @@ static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* t
                     int tie_row = -1) {
   if (t_model < 0 || t_model >= h->T || t_post < 0 || t_post >= h->T)
     return h->fail(-1, "timestep out of range [0,%d)", h->T);  // constrained.py:139
-  for (int off = 0; off < B; off += h->chunk) {
-    const int Bc = std::min(h->chunk, B - off);
-    int rc = denoise_chunk(h, ws, tin + (size_t)off * h->S, t_model, Bc, st, skip_embed);
+  for (int off = 0; off < B; off += h->plan.chunk) {
+    const int Bc = std::min(h->plan.chunk, B - off);
+    int rc = denoise_chunk(h, ws, tin + (size_t)off * h->plan.S, t_model, Bc, st, skip_embed);
     if (rc) return rc;
     PostArgs p{};
     fill_post(h, p, cond, s, off, Bc);
     p.logits = ws.logits;
-    p.ldl = h->Cp;
-    p.tokens = tin + (size_t)off * h->S;
+    p.ldl = h->plan.Cp;
+    p.tokens = tin + (size_t)off * h->plan.S;
     p.t_post = t_post;
     p.step = step;
     p.layout_off = (int)(rng_layout_off + off);
+    // the launch that draws the step's tokens also writes the next step's embedding rows (one chunk per call: run_loop_body)
+    auto embed_into = [&](PostArgs& q) {
+      if (embed_next) { q.x_next = ws.P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D; }
+    };
     // cond=relation adjusts the log-probabilities only while t >= 10 (logit_adjustment.py:107); the remaining steps are
     // a plain constrained step with the [PAD] disable, i.e. the fused posterior + draw launch
     const bool adjust = rel && t_model >= 10 && rel->num_update > 0;
     if (!adjust) {
       if (rel) p.pad_disable = 1;
-      p.tokens_out = tout + (size_t)off * h->S;
-      if (embed_next) {  // (one chunk per call: run_loop_body)
-        p.x_next = ws.P; p.emb = h->emb; p.pos = h->pos; p.D = h->D; p.ldx = h->D;
-      }
+      p.tokens_out = tout + (size_t)off * h->plan.S;
+      embed_into(p);
       if (tie_row >= 0 && h->tie_rel > 0.f && h->tie_flags && s->kind == LDM_SAMPLE_DETERMINISTIC) {
         p.tie_flags = h->tie_flags + (size_t)tie_row * h->cfg.max_batch + rng_layout_off + off;
         p.tie_rel = h->tie_rel;
         p.tie_abs = h->tie_abs;
       }
-      ldm_handle::Scope sc(h, st, "posterior_sample", 0, (double)Bc * h->S * (h->Cp * 4 + 8));
+      ldm_handle::Scope sc(h, st, "posterior_sample", 0, (double)Bc * h->plan.S * (h->plan.Cp * 4 + 8));
       launch_posterior_sample(p, st);
       continue;
     }
@@ -139,14 +141,12 @@ static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* t
     if (relation_step_supported(p)) {  // ... in ONE launch (r04)
       PostArgs q = p;
       q.pad_disable = 1;
-      q.tokens_out = tout + (size_t)off * h->S;
-      if (embed_next) {
-        q.x_next = ws.P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
-      }
+      q.tokens_out = tout + (size_t)off * h->plan.S;
+      embed_into(q);
       RelArgs a{};
-      a.cond_seq = cond->d_cond_seq + (size_t)off * h->S;
+      a.cond_seq = cond->d_cond_seq + (size_t)off * h->plan.S;
       fill_rel(h, a, rel, rel_layout_off + off, Bc);
-      ldm_handle::Scope sc(h, st, "relation_step", 0, (double)Bc * h->S * (h->Cp * 4 + 8));
+      ldm_handle::Scope sc(h, st, "relation_step", 0, (double)Bc * h->plan.S * (h->plan.Cp * 4 + 8));
       launch_relation_step(q, a, st);
       continue;
     }
@@ -157,14 +157,14 @@ static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* t
       q.logp_out = ws.rel_logp;
       q.logp_tm = 1;  // (the handle's own buffer: token-major, a token's classes contiguous)
       q.tokens_out = nullptr;
-      ldm_handle::Scope sc(h, st, "posterior", 0, (double)Bc * h->S * (h->Cp * 4 + h->C * 4));
+      ldm_handle::Scope sc(h, st, "posterior", 0, (double)Bc * h->plan.S * (h->plan.Cp * 4 + h->plan.C * 4));
       launch_posterior_sample(q, st);
     }
     {
       RelArgs a{};
       a.logp = ws.rel_logp;
       a.logp_tm = 1;
-      a.cond_seq = cond->d_cond_seq + (size_t)off * h->S;
+      a.cond_seq = cond->d_cond_seq + (size_t)off * h->plan.S;
       fill_rel(h, a, rel, rel_layout_off + off, Bc);
       ldm_handle::Scope sc(h, st, "relation_update", 0, (double)Bc * 4 * h->cfg.n_bin * h->cfg.max_elem * 8);
       launch_relation_update(a, st);
@@ -177,13 +177,11 @@ static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* t
       q.pad_disable = 1;
       q.logp_in = ws.rel_logp;
       q.logp_tm = 1;
-      q.tokens_out = tout + (size_t)off * h->S;
+      q.tokens_out = tout + (size_t)off * h->plan.S;
       q.step = step;
       q.layout_off = (int)(rng_layout_off + off);
-      if (embed_next) {  // the next step's embedding rows, as in the fused launch above
-        q.x_next = ws.P; q.emb = h->emb; q.pos = h->pos; q.D = h->D; q.ldx = h->D;
-      }
-      ldm_handle::Scope sc(h, st, "pad_disable_sample", 0, (double)Bc * h->S * (h->C * 4 + 8));
+      embed_into(q);
+      ldm_handle::Scope sc(h, st, "pad_disable_sample", 0, (double)Bc * h->plan.S * (h->plan.C * 4 + 8));
       launch_posterior_sample(q, st);
     }
   }
@@ -197,23 +195,17 @@ static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* t
 // vocabulary head, so the adjusted steps run posterior -> SGD -> [PAD] disable -> draw in the same launch
 // (stack_stream_k<., 2, true>); needs the constrained vocabulary with <= 32 bins and <= 32 elements.
 bool ldm_host::loop_fusable(const ldm_handle* h, const ldm_relation* rel) {
-  int live_max = 0;
-  for (int a = 0; a < h->cfg.n_attr; ++a) live_max = std::max(live_max, h->vocab.count[a] + 2);
-  if (rel && (h->rel_loop == 0 || h->cfg.q_type != LDM_Q_CONSTRAINED || h->cfg.n_bin > 32 || h->cfg.max_elem > 32 ||
-              h->cfg.n_attr != 5))
-    return false;
-  // (C - 1 > 128: the row log-softmax guards `class < C - 1` in the last of the five head tiles only; n_attr == 5 is ldm_create's)
-  return h->stack_loop && h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6 && h->head_img_ks && h->Cp == 160 && h->C - 1 > 128 && live_max <= kStackPostMaxLive && h->S <= 128 &&
-         h->T < 32768 && !h->fast.empty() && h->tbl_att_dyn && h->D == 464 && h->F <= 2048;
+  // (the geometry half: ldm_engine_plan.h loop_geometry / rel_loop_geometry; here what ldm_finalize_weights has to have built)
+  return (rel ? h->plan.rel_loop_geometry : h->plan.loop_geometry) && h->head_img_ks && !h->fast.empty() && h->tbl_att_dyn;
 }
 
 // The step-0 logits table of (t0, S) for a launch on `st` (ldm_handle.h Step0Entry), built on first use; *tab = nullptr
 // where this call has to run without it: the cache is off, the stream is being captured and the table is not known to be
 // complete (the build must not be recorded into the caller's graph), or another stream's build is still in flight.
-static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& hd, int t0, int t_post0, hipStream_t st,
+static int step0_table(ldm_handle* h, const StackWeights& sw, int t0, int t_post0, hipStream_t st,
                        const float** tab) {
   *tab = nullptr;
-  if (!h->step0_cache || !h->step0_tab) return 0;
+  if (!h->plan.step0_cache || !h->step0_tab) return 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   bool capturing = false;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) {  // (e.g. the null stream while another stream captures globally)
@@ -223,7 +215,7 @@ static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& 
     capturing = cs != hipStreamCaptureStatusNone;
   }
   for (auto& e : h->step0) {
-    if (e.t != t0 || e.S != h->S) continue;
+    if (e.t != t0 || e.S != h->plan.S) continue;
     if (!e.settled && !capturing && hipEventQuery(h->step0_ev[e.slot]) == hipSuccess) e.settled = true;
     (void)hipGetLastError();  // (hipErrorNotReady is not an error of this call)
     if (e.settled || (!capturing && e.built_on == st)) *tab = h->step0_tab + (size_t)e.slot * kStackStep0Floats;
@@ -231,8 +223,8 @@ static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& 
   }
   if (capturing) return 0;
   ldm_handle::Step0Entry e;
-  e.t = t0; e.S = h->S; e.built_on = st;
-  if ((int)h->step0.size() >= ldm_handle::kStep0Slots) {  // replace the oldest, once no launch of any stream can still read it
+  e.t = t0; e.S = h->plan.S; e.built_on = st;
+  if ((int)h->step0.size() >= kStep0Slots) {  // replace the oldest, once no launch of any stream can still read it
     e.slot = h->step0.front().slot;
     h->step0.erase(h->step0.begin());
     HIP_OK(h, hipDeviceSynchronize());
@@ -247,17 +239,17 @@ static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& 
   PostArgs p{};
   fill_post(h, p, nullptr, &det, 0, 1);
   p.tokens = h->step0_tok;
-  p.tokens_out = h->step0_tok + h->S;
+  p.tokens_out = h->step0_tok + h->plan.S;
   p.emb = h->emb; p.pos = h->pos; p.D = h->D;
   const int32_t tm = t0, tp = t_post0;
   StackLoop lp{};
-  lp.tables = StackTables{h->tbl_att_static, h->tbl_att_dyn, h->tbl_ffn, h->tbl_head};
+  lp.tables = sw.tables;
   lp.post = &p; lp.adaln = h->adaln; lp.t_model = &tm; lp.t_post = &tp;
   lp.n_steps = 1; lp.inter_ld = 1; lp.tie_ld = h->cfg.max_batch;
   lp.logits0_out = h->step0_tab + (size_t)e.slot * kStackStep0Floats;
   {
     ldm_handle::Scope sc(h, st, "step0_logits_build", 0, (double)kStackStep0Floats * 4);
-    launch_stack_loop(ls, h->F, h->D, 1, h->S, h->H, h->dh, hd, lp, st);
+    launch_stack_loop(sw.ls, h->F, h->D, 1, h->plan.S, h->H, h->plan.dh, sw.head, lp, st);
   }
   HIP_OK(h, hipEventRecord(h->step0_ev[e.slot], st));
   h->step0.push_back(e);
@@ -272,21 +264,14 @@ static int step0_table(ldm_handle* h, const FusedLayerSet& ls, const StackHead& 
 static int run_loop_fused(ldm_handle* h, const int32_t* tin, int32_t* tout, const ldm_cond* cond, const ldm_relation* rel,
                           const int32_t* t_model, const int32_t* t_post, int n_steps, const ldm_sampler* s, int step0, int B,
                           int32_t* d_inter, int tie_row0, hipStream_t st, bool from_start = false) {
-  const int D = h->D, F = h->F, M = B * h->S;
-  FusedLayerSet ls{};
-  ls.n_layer = h->L;
-  for (int i = 0; i < h->L; ++i) {
-    const LayerW& w = h->layers[i];
-    ls.w[i] = FusedLayerW{h->fast[i].attn_head_img_ks, h->fast[i].b_in, nullptr, nullptr, h->fast[i].b_out_v,
-                          h->fast[i].ffn_img_pipe, w.b1, w.b2, w.g2, w.be2};
-  }
-  const StackHead hd{h->head_img_ks, h->head_g, h->head_b, nullptr, h->Cp, h->Cp / 32};
+  const int D = h->D, F = h->F, M = B * h->plan.S;
+  const StackWeights sw = stack_weights(h, -1, nullptr);   // (the AdaLN rows of a step come from the kernel's tables)
   // (the roofline stays against the algorithmic work: n * step_flops, although the first pass of an all-[MASK] layout is a table read)
-  const double step_flops = h->L * (gemm_flops(M, 3 * D, D) + 4.0 * B * h->H * (double)h->S * h->S * h->dh +
-                                    gemm_flops(M, D, D) + 2 * gemm_flops(M, F, D)) + gemm_flops(M, h->C, D);
+  const double step_flops = h->L * (gemm_flops(M, 3 * D, D) + 4.0 * B * h->H * (double)h->plan.S * h->plan.S * h->plan.dh +
+                                    gemm_flops(M, D, D) + 2 * gemm_flops(M, F, D)) + gemm_flops(M, h->plan.C, D);
   const float* logits0 = nullptr;
   if (from_start && h->step0_flags) {
-    int rc = step0_table(h, ls, hd, t_model[0], t_post[0], st, &logits0);
+    int rc = step0_table(h, sw, t_model[0], t_post[0], st, &logits0);
     if (rc) return rc;
     HIP_OK(h, hipMemsetAsync(h->step0_flags, 0, (size_t)B, st));
   }
@@ -310,16 +295,16 @@ static int run_loop_fused(ldm_handle* h, const int32_t* tin, int32_t* tout, cons
       p.tie_abs = h->tie_abs;
     }
     StackLoop lp{};
-    lp.tables = StackTables{h->tbl_att_static, h->tbl_att_dyn, h->tbl_ffn, h->tbl_head};
+    lp.tables = sw.tables;
     lp.post = &p; lp.adaln = h->adaln; lp.t_model = t_model + i0; lp.t_post = t_post + i0;
-    lp.inter = d_inter ? d_inter + (size_t)i0 * B * h->S : nullptr;
+    lp.inter = d_inter ? d_inter + (size_t)i0 * B * h->plan.S : nullptr;
     lp.n_steps = n; lp.inter_ld = B; lp.tie_ld = h->cfg.max_batch;
     lp.rel = rel ? &ra : nullptr;
     // (only the first segment of a call can start all-[MASK]; the kernel tests the tokens itself either way)
     lp.logits0 = i0 == 0 ? logits0 : nullptr;
     lp.step0_flags = i0 == 0 && from_start ? h->step0_flags : nullptr;
-    ldm_handle::Scope sc(h, st, "layers_fused_loop", n * step_flops, (double)B * h->S * 8);
-    launch_stack_loop(ls, F, D, B, h->S, h->H, h->dh, hd, lp, st);
+    ldm_handle::Scope sc(h, st, "layers_fused_loop", n * step_flops, (double)B * h->plan.S * 8);
+    launch_stack_loop(sw.ls, F, D, B, h->plan.S, h->H, h->plan.dh, sw.head, lp, st);
   }
   return 0;
 }
@@ -368,18 +353,18 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
                          int lane, hipStream_t st) {
   // state lives in tok_a / tok_b (ping-pong); chunk-major order keeps one chunk's activations and the
   // weights resident in L2 / Infinity Cache for all T steps before moving to the next chunk
-  const size_t S = h->S;
+  const size_t S = h->plan.S;
   // BALANCED chunks (r06): a call of B layouts needs ceil(B / chunk) passes; they share the layouts evenly — 300 layouts are 150 + 150, not 256 + 44
   // (the 44-layout pass kept 212 of 256 compute units idle for as long as the full one; a call's two passes also overlap on the lanes when each
   // fills only part of the chip: same-box split 1 012 -> 1 105, hybrid 1 818 -> 2 011 layouts/s at B = 300; + 6 % / + 1 % at B = 400).  Tokens do not depend on the cut
   // (B = 300 as 150 + 150: tests/test_hip_parity.py test_split_mode_loop_properties, tests/test_r04_parity.py test_relation_in_the_loop_kernel_equals_the_per_step_path).
   // Only where the remainder is small: with a remainder of >= 3/4 of a chunk the uneven cut is 2 % FASTER for the short hybrid launches (488 = 256 + 232: 2 142
   // against 2 093 for 244 + 244 — passes of unequal length drift against each other on the lanes instead of running in lock-step; profiles/r06_call16_17_25_*).
-  const int n_pass = (B + h->chunk - 1) / h->chunk;
-  const int rem = B - (n_pass - 1) * h->chunk;
-  const int cb = (h->balanced_chunks && n_pass > 1 && 4 * rem < 3 * h->chunk) ? (B + n_pass - 1) / n_pass : h->chunk;
+  const int n_pass = (B + h->plan.chunk - 1) / h->plan.chunk;
+  const int rem = B - (n_pass - 1) * h->plan.chunk;
+  const int cb = (h->plan.balanced_chunks && n_pass > 1 && 4 * rem < 3 * h->plan.chunk) ? (B + n_pass - 1) / n_pass : h->plan.chunk;
   const int first = lane < 0 ? 0 : lane * cb;
-  const int stride = lane < 0 ? cb : h->n_lanes * cb;
+  const int stride = lane < 0 ? cb : h->plan.n_lanes * cb;
   Workspace& ws = h->ws[lane < 0 ? 0 : lane];
   for (int off = first; off < B; off += stride) {
     const int Bc = std::min(cb, B - off);
@@ -388,13 +373,13 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
       cc = *cond;
       if (cc.d_cond_seq) cc.d_cond_seq += off * S;
       if (cc.d_strong_mask) cc.d_strong_mask += off * S;
-      if (cc.d_weak_logits) cc.d_weak_logits += (size_t)off * h->C * S;
+      if (cc.d_weak_logits) cc.d_weak_logits += (size_t)off * h->plan.C * S;
     }
     int32_t* cur = h->tok_a + off * S;
     int32_t* nxt = h->tok_b + off * S;
     // the stack kernel takes raw rows and computes its own row statistics, so the posterior kernel of step i can write
     // step i + 1's embedding itself (no separate embedding launch inside the loop)
-    const bool fuse_embed = h->cfg.precision == LDM_PREC_FAST_F16 && h->fused_attn == 6;
+    const bool fuse_embed = h->plan.structure == Structure::Stack;
     for (int i = 0; i < n_steps; ++i) {
       int rc = step_all(h, ws, cur, nxt, t_model[i], t_post[i], cond ? &cc : nullptr, rel, off, s, i, Bc, off, st,
                         fuse_embed && i > 0, fuse_embed && i + 1 < n_steps, i);
@@ -425,7 +410,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
   ON_DEVICE(h);
   if ((rc = check_relation(h, rel, cond, B))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const size_t nbytes = (size_t)B * h->S * 4;
+  const size_t nbytes = (size_t)B * h->plan.S * 4;
   HIP_OK(h, hipEventRecord(h->loop_a, st));
   if ((rc = set_rng(h, seed, first_layout, st))) return rc;
   if ((rc = tie_begin(h, s, rel, n_steps, B, st))) return rc;
@@ -445,7 +430,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
     // fixed addresses and is reused across batches whose cond tensors live elsewhere
     ldm_cond staged{};
     if (cond) {
-      const size_t nS = (size_t)B * h->S;
+      const size_t nS = (size_t)B * h->plan.S;
       staged.pad_disable = cond->pad_disable;
       if (cond->d_cond_seq) {
         HIP_OK(h, hipMemcpyAsync(h->st_cond_seq, cond->d_cond_seq, nS * 4, hipMemcpyDeviceToDevice, st));
@@ -456,8 +441,8 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
         staged.d_strong_mask = h->st_strong;
       }
       if (cond->d_weak_logits) {
-        if (!h->st_weak && (rc = h->dalloc(&h->st_weak, (size_t)h->cfg.max_batch * h->C * h->S, false))) return rc;
-        HIP_OK(h, hipMemcpyAsync(h->st_weak, cond->d_weak_logits, nS * h->C * 4, hipMemcpyDeviceToDevice, st));
+        if (!h->st_weak && (rc = h->dalloc(&h->st_weak, (size_t)h->cfg.max_batch * h->plan.C * h->plan.S, false))) return rc;
+        HIP_OK(h, hipMemcpyAsync(h->st_weak, cond->d_weak_logits, nS * h->plan.C * 4, hipMemcpyDeviceToDevice, st));
         staged.d_weak_logits = h->st_weak;
       }
       cond = &staged;
@@ -522,7 +507,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
     int32_t* inter_dst = nullptr;
     if (d_intermediates) {
       if (n_steps > h->T) return h->fail(-1, "intermediates: n_steps %d > T %d", n_steps, h->T);
-      if (!h->st_inter && (rc = h->dalloc(&h->st_inter, (size_t)h->T * h->cfg.max_batch * h->S, false))) return rc;
+      if (!h->st_inter && (rc = h->dalloc(&h->st_inter, (size_t)h->T * h->cfg.max_batch * h->plan.S, false))) return rc;
       inter_dst = h->st_inter;
     }
     key.has_inter = inter_dst != nullptr;
@@ -542,8 +527,8 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
     for (auto& g : h->graphs)
       if (g.key == key) ge = &g;
     // lanes that actually own a chunk of this call
-    const int n_chunks = (B + h->chunk - 1) / h->chunk;
-    const int lanes = std::min(h->n_lanes, n_chunks);
+    const int n_chunks = (B + h->plan.chunk - 1) / h->plan.chunk;
+    const int lanes = std::min(h->plan.n_lanes, n_chunks);
     if (!ge) {
       if (h->graphs.size() >= 8) {  // small LRU-less cache: drop the oldest
         h->graphs[0].destroy();
@@ -556,7 +541,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
         hipStream_t cap = nullptr;
         HIP_OK(h, hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
         HIP_OK(h, hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-        if (lane > 0 && h->lane_offset_us > 0) launch_delay_us(lane * h->lane_offset_us, cap);
+        if (lane > 0 && h->plan.lane_offset_us > 0) launch_delay_us(lane * h->plan.lane_offset_us, cap);
         rc = run_loop_body(h, cond, rel, h_t_model, h_t_post, n_steps, s, B, inter_dst, lanes > 1 ? lane : -1, cap);
         hipGraph_t graph = nullptr;
         hipError_t e = hipStreamEndCapture(cap, &graph);
@@ -589,7 +574,7 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
     HIP_OK(h, hipGraphLaunch(ge->exec[0], st));
     for (size_t lane = 1; lane < ge->exec.size(); ++lane) HIP_OK(h, hipStreamWaitEvent(st, h->lane_done[lane], 0));
     if (inter_dst)
-      HIP_OK(h, hipMemcpyAsync(d_intermediates, inter_dst, (size_t)n_steps * B * h->S * 4, hipMemcpyDeviceToDevice, st));
+      HIP_OK(h, hipMemcpyAsync(d_intermediates, inter_dst, (size_t)n_steps * B * h->plan.S * 4, hipMemcpyDeviceToDevice, st));
   } else {
     if ((rc = run_loop_body(h, cond, rel, h_t_model, h_t_post, n_steps, s, B, d_intermediates, -1, st))) return rc;
   }

@@ -25,7 +25,7 @@ int err_end(ldm_handle* h, hipStream_t st) {
   HIP_OK(h, hipGetLastError());
   HIP_OK(h, hipMemcpyAsync(&e, h->vb_err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
   HIP_OK(h, hipStreamSynchronize(st));
-  if (e & ldm_vb::kErrRange) return h->fail(-6, "a token is outside [0, %d)", h->C);
+  if (e & ldm_vb::kErrRange) return h->fail(-6, "a token is outside [0, %d)", h->plan.C);
   if (e & ldm_vb::kErrMaskX0) return h->fail(-6, "x_0 holds [MASK] (%d): only noised states do", h->vocab.mask_id);
   if (e & ldm_vb::kErrSubVocab) return h->fail(-6, "a token is not of its position's sub-vocabulary (attribute body, [PAD], [MASK])");
   return 0;
@@ -35,9 +35,9 @@ void fill_vb(const ldm_handle* h, VbArgs& p, int t, int B) {
   p.sched = h->sched;
   p.T = h->T;
   p.t = t;
-  p.f32_lse = h->cfg.precision == LDM_PREC_FAST_F16 ? 1 : 0;
+  p.f32_lse = h->plan.fast() ? 1 : 0;
   p.B = B;
-  p.S = h->S;
+  p.S = h->plan.S;
   p.v = h->vocab;
   p.err = h->vb_err;
 }
@@ -112,7 +112,7 @@ int vb_terms(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const in
   VbArgs p{};
   fill_vb(h, p, c, 0, B);
   p.logits = d_logits;
-  p.ldl = h->C;
+  p.ldl = h->plan.C;
   p.x0 = d_x0;
   p.xt = d_xt;
   p.sums = d_sums;
@@ -144,14 +144,14 @@ int vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, cons
     d_xt = h->tok_a;
   }
   Workspace& ws = h->ws[0];
-  for (int off = 0; off < B; off += h->chunk) {
-    const int Bc = std::min(h->chunk, B - off);
-    const size_t ro = (size_t)off * h->S;
+  for (int off = 0; off < B; off += h->plan.chunk) {
+    const int Bc = std::min(h->plan.chunk, B - off);
+    const size_t ro = (size_t)off * h->plan.S;
     if ((rc = denoise_chunk(h, ws, d_xt + ro, c.t, Bc, st, false, c.d_t ? c.d_t + off : nullptr))) return rc;
     VbArgs p{};
     fill_vb(h, p, c, off, Bc);
     p.logits = ws.logits;
-    p.ldl = h->Cp;
+    p.ldl = h->plan.Cp;
     p.x0 = d_x0 + ro;
     p.xt = d_xt + ro;
     p.sums = d_sums + (size_t)off * ldm_vb::kNumSums;

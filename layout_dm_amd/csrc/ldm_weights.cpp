@@ -60,7 +60,7 @@ static int need(ldm_handle* h, const std::string& key, std::initializer_list<int
 // split — lo is stored unscaled (kSplitLoScale = 1) and fp16's denormal spacing 2^-24 must be small against the weights — and
 // *out_scale = 2^-k goes to the GEMM's epilogue.
 static int make_w16(ldm_handle* h, const float* w, int N, int K, int Kp, __half** hi, __half** lo, float* out_scale = nullptr) {
-  const bool split = h->cfg.precision == LDM_PREC_SPLIT_F16;
+  const bool split = h->plan.split_type();
   float scale = 1.0f;
   if (split) {
     std::vector<float> host((size_t)N * K);
@@ -148,7 +148,7 @@ static int make_x3_kstep(ldm_handle* h, const __half* hi, const __half* lo, int 
   HIP_OK(h, hipDeviceSynchronize());  // (the cast kernels of make_w16)
   HIP_OK(h, hipMemcpy(a.data(), hi, n * 2, hipMemcpyDeviceToHost));
   HIP_OK(h, hipMemcpy(b.data(), lo, n * 2, hipMemcpyDeviceToHost));
-  const std::vector<uint16_t> img = ldm_pack::pack_x3_kstep_image(a.data(), b.data(), N, ld, h->H, h->dh);
+  const std::vector<uint16_t> img = ldm_pack::pack_x3_kstep_image(a.data(), b.data(), N, ld, h->H, h->plan.dh);
   __half* d = nullptr;
   int rc = h->dalloc(&d, img.size(), false);
   if (rc) return rc;
@@ -204,14 +204,14 @@ static int upload_image(ldm_handle* h, const std::vector<uint16_t>& img, void** 
 // (index maps and image packers: ldm_pack.h — pure C++, unit-tested on the CPU by tests/cpu_pack_check.cpp)
 
 static int build_fast_weights(ldm_handle* h) {
-  const int D = h->D, F = h->F, C = h->C, H = h->H, dh = h->dh, HD = h->HD, Dq = h->Dq, Fq = h->Fq;
+  const int D = h->D, F = h->F, C = h->plan.C, H = h->H, dh = h->plan.dh, HD = h->plan.HD, Dq = h->plan.Dq, Fq = h->plan.Fq;
   auto id = [](int x) { return x; };
   // in_proj row n = which*D + head*dh + d  ->  (which*H + head)*64 + d   (head slices padded to 64)
   auto qkv_row = [=](int n) { return ldm_pack::qkv_row(n, D, H, dh); };
   // out_proj column k = head*dh + d -> head*64 + d (matches the attention kernel's output layout)
   auto head_col = [=](int k) { return ldm_pack::head_col(k, dh); };
   auto kslot = [](int k) { return ldm_pack::kslot(k); };
-  const bool stack = h->fused_attn == 6;  // (geometry checked in ldm_create)
+  const bool stack = h->plan.structure == Structure::Stack;
   h->fast.assign(h->L, ldm_handle::FastLayer{});
   int rc;
   for (int i = 0; i < h->L; ++i) {
@@ -269,7 +269,7 @@ static int build_fast_weights(ldm_handle* h) {
     if ((rc = pack_w16(h, h->head_w, C, D, round_up(C, 256), Dq, id, kslot, &hk))) return rc;
     const std::vector<uint16_t> hh = download16(h, hk, (size_t)round_up(C, 256) * Dq, &rc);
     if (rc) return rc;
-    return upload_image(h, ldm_pack::pack_head_image(hh.data(), h->Cp / 32), &h->head_img_ks);
+    return upload_image(h, ldm_pack::pack_head_image(hh.data(), h->plan.Cp / 32), &h->head_img_ks);
   }
   return pack_w16(h, h->head_w, C, D, round_up(C, 256), Dq, id, id, &h->fast_head);
 }
@@ -282,7 +282,7 @@ static int build_fast_weights(ldm_handle* h) {
 //   head               kStackTblAttDyn floats      head LayerNorm gamma | beta | 0      (takes the att_dyn slot behind the last layer)
 static int build_loop_tables(ldm_handle* h) {
   const int D = h->D, F = h->F, L = h->L, T = h->T;
-  if (h->fused_attn != 6 || h->H * 64 * 3 != kStackTblAttStatic || D > 512 || F > 2048) return 0;  // not on the stack kernel
+  if (h->plan.structure != Structure::Stack || h->H * 64 * 3 != kStackTblAttStatic || D > 512 || F > 2048) return 0;  // not on the stack kernel
   std::vector<float> ada((size_t)T * L * 2 * D);
   HIP_OK(h, hipDeviceSynchronize());  // (the AdaLN table kernels)
   HIP_OK(h, hipMemcpy(ada.data(), h->adaln, ada.size() * 4, hipMemcpyDeviceToHost));
@@ -336,7 +336,7 @@ static int build_loop_tables(ldm_handle* h) {
 extern "C" int ldm_finalize_weights(ldm_handle* h) {
   if (!h) return -1;
   ON_DEVICE(h);
-  const int D = h->D, F = h->F, C = h->C, T = h->T, L = h->L;
+  const int D = h->D, F = h->F, C = h->plan.C, T = h->T, L = h->L;
   const std::string tr = "transformer.";
   int rc;
   const float *elem = nullptr, *attr = nullptr;
@@ -346,7 +346,7 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
   if ((rc = need(h, tr + "head.0.weight", {D}, &h->head_g))) return rc;
   if ((rc = need(h, tr + "head.0.bias", {D}, &h->head_b))) return rc;
   if ((rc = need(h, tr + "head.1.weight", {C, D}, &h->head_w))) return rc;
-  if (!h->pos && (rc = h->dalloc(&h->pos, (size_t)h->S * D))) return rc;
+  if (!h->pos && (rc = h->dalloc(&h->pos, (size_t)h->plan.S * D))) return rc;
   if (!h->adaln && (rc = h->dalloc(&h->adaln, (size_t)T * L * 2 * D))) return rc;
   // everything below is derived from the checkpoint: drop what an earlier finalize built (nothing may still be running on it),
   // then collect the new allocations in h->derived
@@ -369,7 +369,7 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
     ~Sink() { h->to_derived = false; }
   } sink(h);
   launch_pos_table(elem, attr, h->pos, h->cfg.max_elem, h->cfg.n_attr, D, 0);
-  const bool f16 = h->cfg.precision != LDM_PREC_EXACT_F32;
+  const bool row_resident = h->plan.structure == Structure::RowResident;
   h->layers.assign(L, LayerW{});
   for (int i = 0; i < L; ++i) {
     const std::string b = tr + "backbone.layers." + std::to_string(i) + ".";
@@ -389,27 +389,27 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
     if ((rc = need(h, b + "norm2.weight", {D}, &w.g2))) return rc;
     if ((rc = need(h, b + "norm2.bias", {D}, &w.be2))) return rc;
     launch_adaln_table(emb_t, lin_w, lin_b, h->adaln, T, D, L, i, 0);
-    if (f16 && h->cfg.precision != LDM_PREC_FAST_F16) {
-      if ((rc = make_w16(h, w.w_in, 3 * D, D, h->Dp, &w.w_in16, &w.w_in16lo, &w.s_in))) return rc;
-      if ((rc = make_w16(h, w.w_out, D, D, h->Dp, &w.w_out16, &w.w_out16lo, &w.s_out))) return rc;
-      if ((rc = make_w16(h, w.w1, F, D, h->Dp, &w.w1_16, &w.w1_16lo, &w.s1))) return rc;
-      if ((rc = make_w16(h, w.w2, D, F, h->Fp, &w.w2_16, &w.w2_16lo, &w.s2))) return rc;
-      if (h->lngemm) {
-        if ((rc = make_x3_image(h, w.w_in16, w.w_in16lo, h->x3_qkv_tiles, &w.x3_qkv))) return rc;
-        if ((rc = make_x3_image(h, w.w1_16, w.w1_16lo, h->x3_ffn1_tiles, &w.x3_ffn1))) return rc;
+    if (h->plan.split_type()) {
+      if ((rc = make_w16(h, w.w_in, 3 * D, D, h->plan.Dp, &w.w_in16, &w.w_in16lo, &w.s_in))) return rc;
+      if ((rc = make_w16(h, w.w_out, D, D, h->plan.Dp, &w.w_out16, &w.w_out16lo, &w.s_out))) return rc;
+      if ((rc = make_w16(h, w.w1, F, D, h->plan.Dp, &w.w1_16, &w.w1_16lo, &w.s1))) return rc;
+      if ((rc = make_w16(h, w.w2, D, F, h->plan.Fp, &w.w2_16, &w.w2_16lo, &w.s2))) return rc;
+      if (row_resident) {
+        if ((rc = make_x3_image(h, w.w_in16, w.w_in16lo, h->plan.x3_qkv_tiles, &w.x3_qkv))) return rc;
+        if ((rc = make_x3_image(h, w.w1_16, w.w1_16lo, h->plan.x3_ffn1_tiles, &w.x3_ffn1))) return rc;
       }
-      if (h->attnout) {   // in_proj with head-padded output columns (+ bias), out_proj as per-(head, k16-step) stages
-        const int H = h->H, dh = h->dh;
+      if (h->plan.attnout) {   // in_proj with head-padded output columns (+ bias), out_proj as per-(head, k16-step) stages
+        const int H = h->H, dh = h->plan.dh;
         if ((rc = make_x3_image(h, w.w_in16, w.w_in16lo, 3 * H * 2, &w.x3_qkv_pad, 3 * D, [=](int n) { return ldm_pack::qkv_row(n, D, H, dh); }))) return rc;
         std::vector<float> b(3 * D), bp((size_t)3 * H * 64, 0.f);
         HIP_OK(h, hipMemcpy(b.data(), w.b_in, b.size() * 4, hipMemcpyDeviceToHost));
         for (int n = 0; n < 3 * D; ++n) bp[ldm_pack::qkv_row(n, D, H, dh)] = b[n];
         if ((rc = h->dalloc(&w.b_in_pad, bp.size(), false))) return rc;
         HIP_OK(h, hipMemcpy(w.b_in_pad, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-        if ((rc = make_x3_kstep(h, w.w_out16, w.w_out16lo, D, h->Dp, &w.x3_out_kstep))) return rc;
+        if ((rc = make_x3_kstep(h, w.w_out16, w.w_out16lo, D, h->plan.Dp, &w.x3_out_kstep))) return rc;
       }
-      if (h->lngemm && (rc = make_x3_slab(h, w.w2_16, w.w2_16lo, D, h->Fp, h->Fp, &w.x3_ffn2_slab))) return rc;
-      if (h->ffn_fused) {   // hybrid: the FFN in plain fp16 behind the attention (kernels_attnout.hip) on the fast mode's chunk image — unscaled fp16 weights,
+      if (row_resident && (rc = make_x3_slab(h, w.w2_16, w.w2_16lo, D, h->plan.Fp, h->plan.Fp, &w.x3_ffn2_slab))) return rc;
+      if (h->plan.ffn_fused) {   // hybrid: the FFN in plain fp16 behind the attention (kernels_attnout.hip) on the fast mode's chunk image — unscaled fp16 weights,
                             // K axes in MFMA k-slot order, stage i = W1 tile i | W2 slab i - 1 (ldm_pack::pack_ffn_image_pipelined)
         auto id = [](int x) { return x; };
         auto kslot = [](int k) { return ldm_pack::kslot(k); };
@@ -426,12 +426,12 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
       }
     }
   }
-  if (h->cfg.precision == LDM_PREC_FAST_F16) {
+  if (h->plan.fast()) {
     if ((rc = build_fast_weights(h))) return rc;
     if ((rc = build_loop_tables(h))) return rc;
-  } else if (f16) {
-    if ((rc = make_w16(h, h->head_w, C, D, h->Dp, &h->head_w16, &h->head_w16lo, &h->head_s))) return rc;
-    if (h->lngemm && (rc = make_x3_image(h, h->head_w16, h->head_w16lo, h->x3_head_tiles, &h->x3_head))) return rc;
+  } else if (h->plan.split_type()) {
+    if ((rc = make_w16(h, h->head_w, C, D, h->plan.Dp, &h->head_w16, &h->head_w16lo, &h->head_s))) return rc;
+    if (row_resident && (rc = make_x3_image(h, h->head_w16, h->head_w16lo, h->plan.x3_head_tiles, &h->x3_head))) return rc;
   }
   // schedule buffers are taken from the checkpoint, not recomputed
   static const char* names[kNumSched] = {"log_at",         "log_bt",         "log_ct",       "log_cumprod_at",
