@@ -51,6 +51,17 @@ enum {
                             un-prefixed schedule buffers (categorical_diffusion/vanilla.py) */
 };
 
+/* what a block's first normalisation (norm1) takes its statistics over == the timestep_type of the reference's Block
+ * (models/transformer_utils.py:124-156).  A state dict does not tell the two apart, so the kind is a create-time argument
+ * (ldm_create_variant).  Everything else of a denoiser variant — pos_emb, the *_abs sinusoid, timestep_type None — is
+ * read from the checkpoint's key set by ldm_finalize_weights. */
+enum {
+  LDM_NORM1_LAYER = 0,   /* AdaLayerNorm / nn.LayerNorm: per row over d_model (adalayernorm, adalayernorm_abs, None) */
+  LDM_NORM1_INSTANCE = 1 /* AdaInsNorm = InstanceNorm1d(d_model) over the sequence axis: per (layout, channel) over the
+                            layout's S rows, biased variance, eps 1e-5, no affine (adainnorm, adainnorm_abs).
+                            LDM_PREC_EXACT_F32 / LDM_PREC_SPLIT_F16 only, on the tiled kernels */
+};
+
 /* sampler kinds: trainer/helpers/sampling.py:13-59,81-130 */
 enum {
   LDM_SAMPLE_DETERMINISTIC = 0,
@@ -129,6 +140,10 @@ typedef struct {
  * own configurations (rico25 / publaynet on the 464 / 8 / 1856 backbone, S = 125) run on the layout-resident kernels,
  * every other accepted geometry on generic tiled kernels (same numerics contract, lower throughput). */
 int ldm_create(const ldm_config* cfg, int device, ldm_handle** out);
+/* ldm_create with the norm1 kind (LDM_NORM1_*; additive export, ABI 5).  ldm_create(cfg, ..) is
+ * ldm_create_variant(cfg, LDM_NORM1_LAYER, ..).  LDM_NORM1_INSTANCE in LDM_PREC_FAST_F16 / MIXED / HYBRID fails with -1: the
+ * message names the precision and points to split / exact.  ldm_describe reports norm1=instance (nothing for layer). */
+int ldm_create_variant(const ldm_config* cfg, int norm1_kind, int device, ldm_handle** out);
 void ldm_destroy(ldm_handle* h);
 const char* ldm_last_error(const ldm_handle* h); /* h may be NULL: last create error */
 
@@ -138,7 +153,15 @@ const char* ldm_last_error(const ldm_handle* h); /* h may be NULL: last create e
  * (models/common/util.py:47-57, test.py:144-149).  The handle owns repacked device copies. */
 int ldm_load_weight(ldm_handle* h, const char* key, const float* h_data, const int64_t* shape, int ndim);
 /* builds the (S,D) positional table (nn_lib.py:112-127), the [T][L][2D] AdaLN table
- * (transformer_utils.py:79-81), fp16 weight copies; fails if a required key is missing. */
+ * (transformer_utils.py:79-81), fp16 weight copies; fails if a required key is missing.
+ * The denoiser variant is read from the key set:
+ *   transformer.pos_emb.pos_emb (rows >= S, D)      pos_emb=default (nn_lib.py:73-88): the table is its first S rows;
+ *                                                   exactly one of it and the elem_emb / attr_emb pair must be present
+ *   norm1.emb.weight + norm1.linear.*               adalayernorm / adainnorm (learned timestep embedding)
+ *   norm1.linear.* alone                            adalayernorm_abs / adainnorm_abs: the [T][D] sinusoid of
+ *                                                   SinusoidalPosEmb (transformer_utils.py:34-49) is built on the device
+ *   norm1.weight + norm1.bias                       timestep_type None: the AdaLN table holds scale = w - 1, shift = b at every t
+ *   norm1.emb.<n>.*                                 the *_mlp kinds: refused (the reference itself cannot run them) */
 int ldm_finalize_weights(ldm_handle* h);
 
 /* ---- parity hooks (one stage each) --------------------------------------------------- */

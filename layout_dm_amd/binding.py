@@ -23,7 +23,7 @@ PRECISIONS = {"exact": PREC_EXACT_F32, "fast": PREC_FAST_F16, "split": PREC_SPLI
 SAMPLERS = {"deterministic": 0, "random": 1, "top_p": 2, "top_k": 3, "gumbel": 4}
 
 EXPORTS = (
-    "ldm_create", "ldm_destroy", "ldm_last_error", "ldm_load_weight", "ldm_finalize_weights",
+    "ldm_create", "ldm_create_variant", "ldm_destroy", "ldm_last_error", "ldm_load_weight", "ldm_finalize_weights",
     "ldm_denoise_logits", "ldm_posterior", "ldm_sample_tokens", "ldm_sample_step", "ldm_sample_loop",
     "ldm_decode_layouts", "ldm_relation_update", "ldm_set_tie_report", "ldm_get_tie_flags",
     "ldm_last_loop_ms", "ldm_set_profiling", "ldm_profile_count", "ldm_profile_get", "ldm_profile_reset",
@@ -58,6 +58,11 @@ class LdmConfig(C.Structure):
 
 
 Q_TYPES = {"constrained": 0, "vanilla": 1}  # models/layoutdm.py:20-23
+NORM1_LAYER, NORM1_INSTANCE = 0, 1          # include/ldm_hip.h LDM_NORM1_*
+# timestep_type of the backbone's Block (models/transformer_utils.py:124-132) -> the norm1 kind ldm_create_variant takes.  What else a
+# variant changes (the *_abs sinusoid, None's plain LayerNorm) the library reads from the checkpoint's key set.
+TIMESTEP_TYPES = {"adalayernorm": NORM1_LAYER, "adalayernorm_abs": NORM1_LAYER, None: NORM1_LAYER,
+                  "adainnorm": NORM1_INSTANCE, "adainnorm_abs": NORM1_INSTANCE}
 
 
 class LdmRelation(C.Structure):  # include/ldm_hip.h: ldm_relation
@@ -115,6 +120,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     vp, i32, u64 = C.c_void_p, C.c_int, C.c_uint64
     lib.ldm_abi_version.restype = C.c_int
     lib.ldm_create.argtypes = [C.POINTER(LdmConfig), i32, C.POINTER(vp)]
+    lib.ldm_create_variant.argtypes = [C.POINTER(LdmConfig), i32, i32, C.POINTER(vp)]
     lib.ldm_destroy.argtypes = [vp]
     lib.ldm_destroy.restype = None
     lib.ldm_last_error.argtypes = [vp]
@@ -238,9 +244,12 @@ class Engine:
     def __init__(self, *, n_category: int, n_bin: int = 32, max_elem: int = 25, n_attr: int = 5,
                  d_model: int = 464, n_head: int = 8, d_ff: int = 1856, n_layer: int = 4, n_step: int = 100,
                  precision="exact", max_batch: int = 512, chunk: int = 0, device: Optional[int] = None,
-                 q_type: str = "constrained", lanes: int = 0):
+                 q_type: str = "constrained", lanes: int = 0, timestep_type: Optional[str] = "adalayernorm"):
         if q_type not in Q_TYPES:
             raise NotImplementedError(f"q_type={q_type}: one of {sorted(Q_TYPES)}")
+        if timestep_type not in TIMESTEP_TYPES:
+            raise NotImplementedError(f"timestep_type={timestep_type}: one of {sorted(map(str, TIMESTEP_TYPES))}")
+        self.timestep_type = timestep_type
         if not torch.cuda.is_available():
             raise RuntimeError("layout_dm_amd needs a ROCm GPU (MI355X); there is no CPU path")
         self.lib = load_library()
@@ -257,7 +266,10 @@ class Engine:
         self.pad_id, self.mask_id = self.C - 2, self.C - 1
         self.max_batch = max_batch
         h = C.c_void_p()
-        rc = self.lib.ldm_create(C.byref(self.cfg), self.device_index, C.byref(h))
+        if TIMESTEP_TYPES[timestep_type] == NORM1_LAYER:
+            rc = self.lib.ldm_create(C.byref(self.cfg), self.device_index, C.byref(h))
+        else:
+            rc = self.lib.ldm_create_variant(C.byref(self.cfg), TIMESTEP_TYPES[timestep_type], self.device_index, C.byref(h))
         if rc != 0:
             raise RuntimeError(f"ldm_create failed ({rc}): {self.lib.ldm_last_error(None).decode()}")
         self._h = h

@@ -7,6 +7,7 @@
 //   AdaLayerNorm  trainer/models/transformer_utils.py:72-83  (LN without affine, eps 1e-5)
 //   LayerNorm     torch.nn.LayerNorm(d, eps=1e-5) (transformer_utils.py:156, nn_lib.py:186-189)
 #include "ldm_kernels.h"
+#include "ldm_variant_core.h"
 
 namespace ldm {
 
@@ -127,6 +128,79 @@ void launch_layernorm(const LnArgs& a, hipStream_t st) {
   }
 }
 
+// ------------------------------------------------------------------ instance norm over a layout's rows (AdaInsNorm)
+// transformer_utils.py:86-100: InstanceNorm1d(D) on x^T — per (layout, channel) mean and biased variance over the layout's S rows, eps
+// 1e-5, no affine — then the AdaLN row: y = x_hat * (1 + scale) + shift.  LnArgs as ln_rows takes them (ada = 1; stats_out / raw unused).
+// One workgroup of kInGroups x kInCols threads per layout: thread (g, tx) owns channels tx, tx + kInCols, ... and rows g, g + kInGroups, ...
+// of them, so a wavefront reads 64 consecutive floats of one row.  Two passes in a fixed order, no atomics, any S: each thread adds its
+// rows top to bottom in float64, the kInGroups partial sums of a channel meet in LDS and every thread of the channel adds them g = 0 first
+// (sum -> mean, then the squared distances to that mean -> variance).  The third pass normalises the thread's own rows, so x may be y32.
+// A layout of equal rows: the float64 sums of S equal floats are exact, mean == x, and y is `shift` exactly.
+constexpr int kInCols = 256, kInGroups = 4;
+
+__device__ __forceinline__ float in_load(const LnArgs& a, const int32_t* tok, int row0, int s, int c) {
+  if (tok) return a.emb[(size_t)tok[s] * a.D + c] + a.pos[(size_t)s * a.D + c];
+  return a.x[(size_t)(row0 + s) * a.D + c];
+}
+
+__global__ __launch_bounds__(kInCols * kInGroups) void in_rows(LnArgs a) {
+  extern __shared__ double in_part[];   // [2][kInGroups][D]: partial sums, partial squared distances
+  const int b = blockIdx.x, tx = threadIdx.x % kInCols, g = threadIdx.x / kInCols;
+  const int S = a.S, D = a.D, row0 = b * S;
+  if (row0 + S > a.M) return;   // (uniform over the workgroup; the launcher's grid is M / S)
+  const int32_t* tok = a.tokens ? a.tokens + row0 : nullptr;
+  double* part_sum = in_part;
+  double* part_sq = in_part + (size_t)kInGroups * D;
+  for (int c = tx; c < D; c += kInCols) {
+    double acc = 0.0;
+#pragma unroll 4
+    for (int s = g; s < S; s += kInGroups) acc += (double)in_load(a, tok, row0, s, c);
+    part_sum[g * D + c] = acc;
+  }
+  __syncthreads();
+  const double inv_s = 1.0 / (double)S;
+  for (int c = tx; c < D; c += kInCols) {
+    const double mean = (((part_sum[c] + part_sum[D + c]) + part_sum[2 * D + c]) + part_sum[3 * D + c]) / (double)S;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int s = g; s < S; s += kInGroups) {
+      const double d = (double)in_load(a, tok, row0, s, c) - mean;
+      acc += d * d;
+    }
+    part_sq[g * D + c] = acc;
+  }
+  __syncthreads();
+  const float* ss = a.p0;
+  const float* sh = a.p1;
+  if (a.t_rows) {  // per-layout timesteps: the AdaLN rows of this workgroup's layout
+    ss = a.ada_tab + (size_t)a.t_rows[b] * a.t_stride + a.layer_off;
+    sh = ss + D;
+  }
+  for (int c = tx; c < D; c += kInCols) {
+    const float mean = (float)((((part_sum[c] + part_sum[D + c]) + part_sum[2 * D + c]) + part_sum[3 * D + c]) / (double)S);
+    const float var = (float)((((part_sq[c] + part_sq[D + c]) + part_sq[2 * D + c]) + part_sq[3 * D + c]) * inv_s);   // biased variance
+    const float rstd = 1.0f / sqrtf(var + 1e-5f);
+    const float mul = 1.0f + ss[c], add = sh[c];
+    for (int s = g; s < S; s += kInGroups) {
+      const float y = (in_load(a, tok, row0, s, c) - mean) * rstd * mul + add;
+      const size_t row = (size_t)(row0 + s);
+      if (a.y32) a.y32[row * D + c] = y;
+      if (a.y16) {
+        const __half h = __float2half_rn(y);
+        a.y16[row * a.ld16 + c] = h;
+        if (a.y16lo) a.y16lo[row * a.ld16 + c] = __float2half_rn((y - __half2float(h)) * kLoScale);
+      }
+    }
+  }
+}
+static_assert(kInGroups == 4, "in_rows adds a channel's four partial sums by name");
+
+void launch_instancenorm(const LnArgs& a, hipStream_t st) {
+  const int layouts = a.M / a.S;   // (M = layouts * S: the denoiser's rows are whole layouts)
+  const size_t lds = (size_t)2 * kInGroups * a.D * sizeof(double);   // 29 KiB at d_model 464, 64 KiB at the 1024 ldm_create admits
+  hipLaunchKernelGGL(in_rows, dim3(layouts), dim3(kInCols * kInGroups), lds, st, a);
+}
+
 // ------------------------------------------------------------------ casts
 __global__ __launch_bounds__(256) void cast_f32_f16(const float* __restrict__ src, __half* __restrict__ dst,
                                                     __half* __restrict__ dstlo, int64_t n, float scale) {
@@ -171,6 +245,39 @@ void launch_adaln_table(const float* emb, const float* w, const float* b, float*
                         hipStream_t st) {
   const int n = T * 2 * D;
   hipLaunchKernelGGL(adaln_table_k, dim3((n + 3) / 4), dim3(256), 0, st, emb, w, b, out, T, D, L, layer);
+}
+
+// timestep_type *_abs: the [T][D] sinusoid of SinusoidalPosEmb (ldm_variant_core.h) — one thread per (t, k), k < D / 2: the sine and the
+// cosine of one argument
+__global__ __launch_bounds__(256) void sinus_table_k(float* __restrict__ out, int T, int D) {
+  const int half = D >> 1;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= T * half) return;
+  const int t = i / half, k = i % half;
+  float s, c;
+  ldm_variant::sinusoid_pair(t, T, k, half, &s, &c);
+  out[(size_t)t * D + k] = s;
+  out[(size_t)t * D + half + k] = c;
+}
+
+void launch_sinus_table(float* out, int T, int D, hipStream_t st) {
+  const int n = T * (D >> 1);
+  hipLaunchKernelGGL(sinus_table_k, dim3((n + 255) / 256), dim3(256), 0, st, out, T, D);
+}
+
+// timestep_type None: out[t][layer][j] = (j < D ? w[j] - 1 : b[j - D]) at every t
+__global__ __launch_bounds__(256) void adaln_const_table_k(const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ out,
+                                                           int T, int D, int L, int layer) {
+  const int two_d = 2 * D;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= T * two_d) return;
+  const int t = i / two_d, j = i % two_d;
+  out[((size_t)t * L + layer) * two_d + j] = ldm_variant::const_row_entry(w, b, D, j);
+}
+
+void launch_adaln_const_table(const float* w, const float* b, float* out, int T, int D, int L, int layer, hipStream_t st) {
+  const int n = T * 2 * D;
+  hipLaunchKernelGGL(adaln_const_table_k, dim3((n + 255) / 256), dim3(256), 0, st, w, b, out, T, D, L, layer);
 }
 
 __global__ __launch_bounds__(256) void pos_table_k(const float* __restrict__ elem, const float* __restrict__ attr,

@@ -24,7 +24,9 @@ extern "C" const char* ldm_last_error(const ldm_handle* h) { return h ? h->err.c
 
 // validate -> probe the device -> plan (ldm_engine_plan.h: everything that depends on the configuration and the knobs alone) -> allocate what the
 // plan counts -> streams and events
-extern "C" int ldm_create(const ldm_config* cfg, int device, ldm_handle** out) {
+extern "C" int ldm_create(const ldm_config* cfg, int device, ldm_handle** out) { return ldm_create_variant(cfg, LDM_NORM1_LAYER, device, out); }
+
+extern "C" int ldm_create_variant(const ldm_config* cfg, int norm1_kind, int device, ldm_handle** out) {
   auto bad = [&](const std::string& msg) {
     create_error() = msg;
     return -1;
@@ -43,7 +45,7 @@ extern "C" int ldm_create(const ldm_config* cfg, int device, ldm_handle** out) {
   // again behind each group; plan_engine itself never sees the environment.
   Knobs kn;
   EnginePlan plan;
-  int refused = plan_engine(*cfg, kn, plan, why);
+  int refused = plan_engine(*cfg, kn, plan, why, norm1_kind);
   if (plan.chunk) {   // (decided as far as the chunk: every refusal but an unknown q_type)
     kn.chunk = knob_int("LDM_CHUNK", Knobs::kUnset);
     kn.balanced_chunks = knob_int("LDM_BALANCED_CHUNKS", Knobs::kUnset);
@@ -56,12 +58,12 @@ extern "C" int ldm_create(const ldm_config* cfg, int device, ldm_handle** out) {
       kn.step0_cache = knob_int("LDM_STEP0_CACHE", Knobs::kUnset);
     }
     if (plan.structure == Structure::RowResident) kn.x3_lngemm = knob_int("LDM_X3_LNGEMM", Knobs::kUnset);
-    refused = plan_engine(*cfg, kn, plan, why);
+    refused = plan_engine(*cfg, kn, plan, why, norm1_kind);
     if (plan.hid_panels) kn.x3_hidpanel = knob_int("LDM_X3_HIDPANEL", Knobs::kUnset);
     if (plan.attnout) kn.x3_attnout = knob_int("LDM_X3_ATTNOUT", Knobs::kUnset);
-    refused = plan_engine(*cfg, kn, plan, why);
+    refused = plan_engine(*cfg, kn, plan, why, norm1_kind);
     if (plan.ffn_fused) kn.hyb_ffn = knob_int("LDM_HYB_FFN", Knobs::kUnset);
-    refused = plan_engine(*cfg, kn, plan, why);
+    refused = plan_engine(*cfg, kn, plan, why, norm1_kind);
   }
   if (refused) {
     create_error() = why;
@@ -370,6 +372,11 @@ extern "C" int ldm_describe(const ldm_handle* h, char* buf, int cap) {
     s += (i ? "," : "") + std::to_string(h->step0[i].t) + ":" + std::to_string(h->step0[i].S);
   // the denoiser takes per-layout timesteps (ldm_denoise_logits_t, ldm_vb_step_t): every engine but fast_f16 on the stack kernel
   s += std::string(";per_layout_t=") + (h->plan.per_layout_t() ? "1" : "0");
+  // the denoiser variant, named only where it is not the default (elem_attr positions, adalayernorm): ldm_create_variant's norm1 kind and what
+  // ldm_finalize_weights read from the checkpoint's key set
+  if (h->plan.instance_norm) s += ";norm1=instance";
+  if (h->pos_default) s += ";pos_emb=default";
+  if (h->timestep_kind != ldm_handle::kTimestepLearned) s += std::string(";timestep_emb=") + (h->timestep_kind == ldm_handle::kTimestepAbs ? "abs" : "none");
   s += ";knobs=" + knobs_honoured();
   if (buf && cap > 0) {
     const size_t n = std::min((size_t)cap - 1, s.size());

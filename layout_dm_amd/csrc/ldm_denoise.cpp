@@ -25,6 +25,11 @@ static void layernorm(ldm_handle* h, hipStream_t st, const char* name, int M, co
   if (ada && d_t) { a.t_rows = d_t; a.ada_tab = h->adaln; a.t_stride = h->L * 2 * h->D; a.layer_off = layer * 2 * h->D; }
   a.y32 = y32; a.y16 = y16; a.y16lo = y16lo;
   a.M = M; a.D = h->D; a.S = h->plan.S; a.ld16 = ld16;
+  if (ada && h->plan.instance_norm) {   // norm1 = AdaInsNorm: statistics per (layout, channel) over the layout's rows — three reads of x
+    ldm_handle::Scope sc(h, st, "adainsnorm", 0, (double)M * h->D * (12 + (y32 ? 4 : 0) + (y16 ? 2 : 0)));
+    launch_instancenorm(a, st);
+    return;
+  }
   ldm_handle::Scope sc(h, st, name, 0, (double)M * h->D * (4 + (y32 ? 4 : 0) + (y16 ? 2 : 0)));
   launch_layernorm(a, st);
 }

@@ -97,6 +97,8 @@ struct EnginePlan {
   int Dq = 0, HD = 0, Fq = 0;   // fast: K padded to 64, heads padded to 64
   int x3_qkv_tiles = 0, x3_ffn1_tiles = 0, x3_head_tiles = 0;   // split-type: 32-column tiles of the row-resident launches' weight images
   int chunk = 0, n_lanes = 1, lane_offset_us = 0;
+  bool instance_norm = false;    // norm1 = AdaInsNorm (timestep_type adainnorm / adainnorm_abs: statistics per (layout, channel) over the layout's S rows): the
+                                 // block's first normalisation is the per-layout launch of kernels_norm.hip (in_rows), which only the tiled sequence has
   bool balanced_chunks = true;   // ldm_loop.cpp run_loop_body: a call's passes share its layouts evenly; LDM_DEV=1 LDM_BALANCED_CHUNKS=0: full chunks + a remainder
   size_t panel_rows = 0;         // split-type: rows of a q / k / v (and hidden) panel
   WorkspaceCounts ws;            // per lane
@@ -115,7 +117,7 @@ struct EnginePlan {
     switch (structure) {
       case Structure::Stack: return "stack";
       case Structure::Generic16: return "generic16";
-      case Structure::Tiled: return "tiled_gemm+attn";
+      case Structure::Tiled: return std::string("tiled_gemm+attn") + (instance_norm ? "+instance_norm" : "");
       default:
         return std::string("row_resident_ln_gemm") + (ffn_fused ? "+attn_ffn_fused_fp16" : "+linear2_prologue") +
                (attnout ? "+attn_out_proj_fused" : "+tiled_gemm+attn");
@@ -178,7 +180,9 @@ inline int validate_config(const ldm_config& cfg, const std::string& refused_kno
 // 0 and the plan, or ldm_create's return code and message: validate_config's refusals first, then the decision and what it refuses.
 // A refusal of the decision (the last two below) leaves the plan filled as far as it was decided — geometry, sizes, options: what the
 // configuration was refused on.
-inline int plan_engine(const ldm_config& cfg, const Knobs& kn, EnginePlan& p, std::string& err) {
+// norm1_kind (LDM_NORM1_*, ldm_create_variant; ldm_create: LDM_NORM1_LAYER, which leaves every plan as it was): what a block's first
+// normalisation computes its statistics over.  LDM_NORM1_INSTANCE runs the tiled sequence in exact / split and is refused elsewhere.
+inline int plan_engine(const ldm_config& cfg, const Knobs& kn, EnginePlan& p, std::string& err, int norm1_kind = LDM_NORM1_LAYER) {
   p = EnginePlan{};
   if (int rc = validate_config(cfg, kn.refused, err)) return rc;
   auto bad = [&](const std::string& msg) {
@@ -186,6 +190,13 @@ inline int plan_engine(const ldm_config& cfg, const Knobs& kn, EnginePlan& p, st
     return -1;
   };
   p.precision = cfg.precision;
+  if (norm1_kind != LDM_NORM1_LAYER && norm1_kind != LDM_NORM1_INSTANCE) return bad("unknown norm1 kind");
+  p.instance_norm = norm1_kind == LDM_NORM1_INSTANCE;
+  if (p.instance_norm && p.fp16_engine()) {
+    static const char* names[5] = {"exact", "fast", "split", "mixed", "hybrid"};
+    return bad(std::string("precision ") + names[cfg.precision] +
+               ": timestep_type adainnorm / adainnorm_abs (instance norm over a layout's rows) has no kernel in the fp16 engines; use precision split or exact");
+  }
   const int D = cfg.d_model, F = cfg.d_ff, H = cfg.n_head;
   const int S = p.S = cfg.max_elem * cfg.n_attr, dh = p.dh = D / H;
   const int C = p.C = cfg.n_category + 4 * cfg.n_bin + 2;
@@ -251,7 +262,8 @@ inline int plan_engine(const ldm_config& cfg, const Knobs& kn, EnginePlan& p, st
     p.x3_head_tiles = x3_tiles(p.Cp);
     const bool lngemm = p.Dp == 512 && lngemm16x3_supported(D, 3 * D, p.x3_qkv_tiles) && lngemm16x3_supported(D, F, p.x3_ffn1_tiles) &&
                         lngemm16x3_supported(D, p.Cp, p.x3_head_tiles) && p.x3_qkv_tiles * 32 <= round_up(3 * D, 256) &&
-                        p.x3_ffn1_tiles * 32 <= round_up(F, 256) && p.x3_head_tiles * 32 <= round_up(C, 256) && Knobs::on(kn.x3_lngemm);
+                        p.x3_ffn1_tiles * 32 <= round_up(F, 256) && p.x3_head_tiles * 32 <= round_up(C, 256) && Knobs::on(kn.x3_lngemm) &&
+                        !p.instance_norm;   // (the row-resident launches normalise a ROW: no per-layout statistics there)
     p.structure = lngemm ? Structure::RowResident : Structure::Tiled;
     // linear2 runs as the GEMM PROLOGUE of the row-resident kernel that normalises its sum (kernels_lngemm.hip PRE: the next layer's AdaLN +
     // in_proj, or the head) instead of as a gemm16x3_k launch: 28 us per layer cheaper than the two launches it replaces, +4 % whole-job

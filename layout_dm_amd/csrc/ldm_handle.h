@@ -149,6 +149,10 @@ struct ldm_handle {
   // weights
   std::map<std::string, Raw> raw;
   bool finalized = false;
+  // the denoiser variant ldm_finalize_weights read from the key set (ldm_describe names it where it is not the default)
+  enum { kTimestepLearned = 0, kTimestepAbs = 1, kTimestepNone = 2 };   // norm1.emb.weight | the sinusoid | nn.LayerNorm, constant in t
+  bool pos_default = false;   // transformer.pos_emb.pos_emb instead of the elem_emb / attr_emb pair
+  int timestep_kind = kTimestepLearned;
   std::vector<LayerW> layers;
   float *pos = nullptr, *adaln = nullptr, *sched = nullptr;
   const float *emb = nullptr, *head_g = nullptr, *head_b = nullptr, *head_w = nullptr;

@@ -68,6 +68,9 @@ struct LnArgs {
   int t_stride, layer_off;   // floats: L * 2 D per timestep, layer * 2 D
 };
 void launch_layernorm(const LnArgs& a, hipStream_t st);
+// AdaInsNorm (transformer_utils.py:86-100): the same arguments with ada = 1, statistics per (layout, channel) over the layout's S rows; M a
+// multiple of S, one workgroup per layout; stats_out / raw are not read
+void launch_instancenorm(const LnArgs& a, hipStream_t st);
 
 // ---- GEMM (kernels_gemm.hip):  C[M,N] = epi(A[M,K] * W[N,K]^T + bias) ---------------------
 struct GemmArgs {
@@ -497,6 +500,11 @@ void launch_f32_to_f16(const float* src, __half* dst, __half* dstlo, int64_t n, 
 // AdaLN table: out[t][l][2D] = Linear(SiLU(Emb[t])) (transformer_utils.py:67-69,80)
 void launch_adaln_table(const float* emb /*[T,D]*/, const float* w /*[2D,D]*/, const float* b /*[2D]*/,
                         float* out /*[T, L, 2D] at layer offset*/, int T, int D, int L, int layer, hipStream_t st);
+// timestep_type *_abs: the [T][D] sinusoid that stands in for the learned embedding (ldm_variant_core.h); D even, >= 4
+void launch_sinus_table(float* out /*[T,D]*/, int T, int D, hipStream_t st);
+// timestep_type None: the AdaLN table of one layer from nn.LayerNorm's affine, constant in t: scale = w - 1, shift = b
+void launch_adaln_const_table(const float* w /*[D]*/, const float* b /*[D]*/, float* out /*[T, L, 2D] at layer offset*/, int T, int D, int L,
+                              int layer, hipStream_t st);
 void launch_pos_table(const float* elem /*[E,D]*/, const float* attr /*[A,D]*/, float* pos /*[S,D]*/, int E,
                       int A, int D, hipStream_t st);
 

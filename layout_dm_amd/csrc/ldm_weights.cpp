@@ -1,6 +1,7 @@
 // Host side of libldm_hip.so: the reference checkpoint -> device weights (ldm_load_weight / ldm_finalize_weights): fp32 views,
 // fp16 / split copies, the LDS weight images and parameter tables of the layout-resident kernels (ldm_pack.h).
 #include "ldm_handle.h"
+#include "ldm_variant_core.h"
 
 #include <functional>
 
@@ -339,10 +340,28 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
   const int D = h->D, F = h->F, C = h->plan.C, T = h->T, L = h->L;
   const std::string tr = "transformer.";
   int rc;
-  const float *elem = nullptr, *attr = nullptr;
+  const float *elem = nullptr, *attr = nullptr, *pos_rows = nullptr;
   if ((rc = need(h, tr + "cat_emb.weight", {C, D}, &h->emb))) return rc;
-  if ((rc = need(h, tr + "pos_emb.elem_emb", {h->cfg.max_elem, D}, &elem))) return rc;
-  if ((rc = need(h, tr + "pos_emb.attr_emb", {h->cfg.n_attr, D}, &attr))) return rc;
+  {
+    // pos_emb: ElementPositionalEmbedding (elem_emb + attr_emb, nn_lib.py:91-127) or PositionalEmbedding (one learned table whose first S
+    // rows are the positions, nn_lib.py:73-88) — a checkpoint carries exactly one of the two
+    const bool has_default = h->raw.count(tr + "pos_emb.pos_emb") != 0;
+    const bool has_pair = h->raw.count(tr + "pos_emb.elem_emb") != 0 || h->raw.count(tr + "pos_emb.attr_emb") != 0;
+    if (has_default == has_pair)
+      return h->fail(-4, "checkpoint must carry either %spos_emb.pos_emb (pos_emb=default) or %spos_emb.elem_emb + %spos_emb.attr_emb (pos_emb=elem_attr): %s",
+                     tr.c_str(), tr.c_str(), tr.c_str(), has_default ? "both are present" : "neither is present");
+    if (has_default) {
+      const Raw& r = h->raw[tr + "pos_emb.pos_emb"];
+      if (r.shape.size() != 2 || r.shape[1] != D || r.shape[0] < h->plan.S)
+        return h->fail(-4, "checkpoint key %spos_emb.pos_emb must be (max_token_length >= %d, %d) — does not match the configured geometry", tr.c_str(),
+                       h->plan.S, D);
+      pos_rows = r.d;
+    } else {
+      if ((rc = need(h, tr + "pos_emb.elem_emb", {h->cfg.max_elem, D}, &elem))) return rc;
+      if ((rc = need(h, tr + "pos_emb.attr_emb", {h->cfg.n_attr, D}, &attr))) return rc;
+    }
+    h->pos_default = has_default;
+  }
   if ((rc = need(h, tr + "head.0.weight", {D}, &h->head_g))) return rc;
   if ((rc = need(h, tr + "head.0.bias", {D}, &h->head_b))) return rc;
   if ((rc = need(h, tr + "head.1.weight", {C, D}, &h->head_w))) return rc;
@@ -368,7 +387,33 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
     explicit Sink(ldm_handle* h_) : h(h_) { h->to_derived = true; }
     ~Sink() { h->to_derived = false; }
   } sink(h);
-  launch_pos_table(elem, attr, h->pos, h->cfg.max_elem, h->cfg.n_attr, D, 0);
+  if (pos_rows)
+    HIP_OK(h, hipMemcpyAsync(h->pos, pos_rows, (size_t)h->plan.S * D * sizeof(float), hipMemcpyDeviceToDevice, 0));
+  else
+    launch_pos_table(elem, attr, h->pos, h->cfg.max_elem, h->cfg.n_attr, D, 0);
+  // timestep_type, from layer 0's norm1 keys (every layer must then agree: `need` below names what is missing):
+  //   norm1.emb.weight          adalayernorm / adainnorm          the learned [T][D] embedding
+  //   norm1.linear.* alone      adalayernorm_abs / adainnorm_abs  the sinusoid, built here once for all layers (ldm_variant_core.h)
+  //   norm1.weight / .bias      None                              nn.LayerNorm: the table holds w - 1 | b at every t
+  //   norm1.emb.<n>.*           *_mlp                             refused: the reference feeds the Long timestep to nn.Linear and raises
+  float* sinus = nullptr;
+  {
+    const std::string n1 = tr + "backbone.layers.0.norm1.";
+    for (const auto& kv : h->raw)
+      if (kv.first.compare(0, n1.size() + 4, n1 + "emb.") == 0 && kv.first != n1 + "emb.weight")
+        return h->fail(-4, "checkpoint key %s: timestep_type adalayernorm_mlp / adainnorm_mlp is not supported (the reference cannot run it either: its "
+                           "nn.Linear receives the integer timestep)", kv.first.c_str());
+    const bool plain = h->raw.count(n1 + "weight") != 0, linear = h->raw.count(n1 + "linear.weight") != 0;
+    if (plain && linear) return h->fail(-4, "checkpoint carries both %sweight (timestep_type None) and %slinear.weight (an Ada norm)", n1.c_str(), n1.c_str());
+    h->timestep_kind = plain ? ldm_handle::kTimestepNone : h->raw.count(n1 + "emb.weight") ? ldm_handle::kTimestepLearned : ldm_handle::kTimestepAbs;
+    if (plain && h->plan.instance_norm)
+      return h->fail(-4, "checkpoint key %sweight: timestep_type None is a LayerNorm, but the handle was created with LDM_NORM1_INSTANCE", n1.c_str());
+    if (h->timestep_kind == ldm_handle::kTimestepAbs) {
+      if (!ldm_variant::sinusoid_args_ok(T, D)) return h->fail(-4, "timestep_type *_abs needs an even d_model >= 4");
+      if ((rc = h->dalloc(&sinus, (size_t)T * D))) return rc;
+      launch_sinus_table(sinus, T, D, 0);
+    }
+  }
   const bool row_resident = h->plan.structure == Structure::RowResident;
   h->layers.assign(L, LayerW{});
   for (int i = 0; i < L; ++i) {
@@ -383,12 +428,20 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
     if ((rc = need(h, b + "linear1.bias", {F}, &w.b1))) return rc;
     if ((rc = need(h, b + "linear2.weight", {D, F}, &w.w2))) return rc;
     if ((rc = need(h, b + "linear2.bias", {D}, &w.b2))) return rc;
-    if ((rc = need(h, b + "norm1.emb.weight", {T, D}, &emb_t))) return rc;
-    if ((rc = need(h, b + "norm1.linear.weight", {2 * D, D}, &lin_w))) return rc;
-    if ((rc = need(h, b + "norm1.linear.bias", {2 * D}, &lin_b))) return rc;
+    if (h->timestep_kind == ldm_handle::kTimestepNone) {
+      if ((rc = need(h, b + "norm1.weight", {D}, &lin_w))) return rc;
+      if ((rc = need(h, b + "norm1.bias", {D}, &lin_b))) return rc;
+    } else {
+      if (h->timestep_kind == ldm_handle::kTimestepLearned && (rc = need(h, b + "norm1.emb.weight", {T, D}, &emb_t))) return rc;
+      if ((rc = need(h, b + "norm1.linear.weight", {2 * D, D}, &lin_w))) return rc;
+      if ((rc = need(h, b + "norm1.linear.bias", {2 * D}, &lin_b))) return rc;
+    }
     if ((rc = need(h, b + "norm2.weight", {D}, &w.g2))) return rc;
     if ((rc = need(h, b + "norm2.bias", {D}, &w.be2))) return rc;
-    launch_adaln_table(emb_t, lin_w, lin_b, h->adaln, T, D, L, i, 0);
+    if (h->timestep_kind == ldm_handle::kTimestepNone)
+      launch_adaln_const_table(lin_w, lin_b, h->adaln, T, D, L, i, 0);
+    else
+      launch_adaln_table(emb_t ? emb_t : sinus, lin_w, lin_b, h->adaln, T, D, L, i, 0);
     if (h->plan.split_type()) {
       if ((rc = make_w16(h, w.w_in, 3 * D, D, h->plan.Dp, &w.w_in16, &w.w_in16lo, &w.s_in))) return rc;
       if ((rc = make_w16(h, w.w_out, D, D, h->plan.Dp, &w.w_out16, &w.w_out16lo, &w.s_out))) return rc;

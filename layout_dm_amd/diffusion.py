@@ -23,6 +23,28 @@ _seed_counter = itertools.count()
 # the reference's entry point logs at INFO (trainer/test.py:38); `precision="auto"` says here which engine a checkpoint got and why
 logger = logging.getLogger("layout_dm_amd")
 
+POS_EMBS = ("elem_attr", "default")   # ElementPositionalEmbedding | PositionalEmbedding (nn_lib.py:73-127)
+INSTANCE_NORM_TYPES = ("adainnorm", "adainnorm_abs")
+TIMESTEP_TYPES = ("adalayernorm", "adalayernorm_abs", None) + INSTANCE_NORM_TYPES
+
+
+def check_timestep_type(timestep_type) -> None:
+    """Raises for what Block accepts (transformer_utils.py:124-132) but nobody can run, and for anything else unknown."""
+    if timestep_type in ("adalayernorm_mlp", "adainnorm_mlp"):
+        raise NotImplementedError(
+            f"timestep_type={timestep_type}: not supported, and the reference cannot run it either — its embedding MLP starts with "
+            "nn.Linear(1, d_model / 2) and is fed the integer (Long) timestep, which raises a dtype error on the first forward pass")
+    if timestep_type not in TIMESTEP_TYPES:
+        raise NotImplementedError(f"timestep_type={timestep_type}: one of {sorted(map(str, TIMESTEP_TYPES))}")
+
+
+def variant_name(pos_emb: str, timestep_type) -> Optional[str]:
+    """What names a denoiser variant in reports, or None for the default (elem_attr positions, adalayernorm)."""
+    parts = ([f"pos_emb={pos_emb}"] if pos_emb != "elem_attr" else []) + \
+            ([f"timestep_type={timestep_type}"] if timestep_type != "adalayernorm" else [])
+    return ", ".join(parts) or None
+
+
 FP16_MAX_CLASSES = 192   # ldm_create: fast / mixed / hybrid refuse wider vocabularies; exact / split take up to 576 classes, 128 bins
 # what each engine delivers on one MI355X (Rico25-shaped sequences, T = 100, batch 512; bench.py measures it on the box at hand)
 THROUGHPUT_CLASS = {
@@ -109,7 +131,8 @@ class HipMaskAndReplaceDiffusion:
                  d_model: int = 464, n_head: int = 8, d_ff: int = 1856, n_layer: int = 4,
                  num_timesteps: int = 100, precision: str = "exact", max_batch: int = 512, chunk: int = 0,
                  device: Optional[int] = None, use_graph: bool = True, q_type: str = "constrained", lanes: int = 0,
-                 verifier: str = "split", auxiliary_loss_weight: float = 1e-1):
+                 verifier: str = "split", auxiliary_loss_weight: float = 1e-1, pos_emb: str = "elem_attr",
+                 timestep_type: Optional[str] = "adalayernorm"):
         # q_type: Q_TYPES of models/layoutdm.py:20-23 — "constrained" (constrained.py) or "vanilla" (vanilla.py)
         # precision "fast_verified": the fp16 engine for every sampler, plus an exact (fp32) engine of the same weights
         # that re-decides the near-tie layouts of DETERMINISTIC decoding (layout_dm_amd/verified.py): greedy tokens are
@@ -126,6 +149,15 @@ class HipMaskAndReplaceDiffusion:
         # unconditionally.  In front of it sits "hybrid" (LDM_PREC_HYBRID_F16: mixed with the FFN and the head in plain fp16 — the fp16 error
         # lives on the attention-score path; 2.8e-4 on the fitted checkpoint), so auto's ladder is fast -> hybrid -> mixed -> reference precision,
         # each rung built on first need and held to the same measurement.
+        # pos_emb / timestep_type: the denoiser variants of the reference's constructor (nn_lib.py:73-127, transformer_utils.py:124-156).
+        # The library reads pos_emb, the *_abs sinusoid and timestep_type None from the checkpoint's key set and serves them on every
+        # engine; the two adainnorm kinds (instance norm over a layout's rows: the state dict does not tell them from adalayernorm)
+        # reach ldm_create_variant and run on the reference-precision engines only — auto then IS its verifier engine
+        if pos_emb not in POS_EMBS:
+            raise NotImplementedError(f"pos_emb={pos_emb}: one of {sorted(POS_EMBS)}")
+        check_timestep_type(timestep_type)
+        self.pos_emb, self.timestep_type = pos_emb, timestep_type
+        self.instance_norm = timestep_type in INSTANCE_NORM_TYPES
         self.verified = None
         self._v_fast = None                      # VerifiedGreedy(fp16 engine, verifier)
         self._v_rung: Dict[str, object] = {}     # rung -> VerifiedGreedy(its engine, verifier), built on first need
@@ -141,7 +173,7 @@ class HipMaskAndReplaceDiffusion:
         self._mk = mk = lambda prec, mb=max_batch: Engine(n_category=n_category, n_bin=n_bin, max_elem=max_elem, n_attr=n_attr,
                                  d_model=d_model, n_head=n_head, d_ff=d_ff, n_layer=n_layer, n_step=num_timesteps,
                                  precision=prec, max_batch=mb, chunk=chunk, device=device, q_type=q_type,
-                                 lanes=lanes)
+                                 lanes=lanes, timestep_type=timestep_type)
         # wide vocabularies (64 / 128 bins per coordinate): the fp16 engines stop at FP16_MAX_CLASSES classes (ldm_create), the
         # reference-precision engines at 576.  auto then IS its reference-precision engine — no fp16 engine is built or measured —
         # and every name that needs an fp16 engine is refused with the library's own message
@@ -154,7 +186,14 @@ class HipMaskAndReplaceDiffusion:
                 if "192 classes" not in str(e):
                     raise
                 raise NotImplementedError(str(e)) from e
-        if self.wide_vocab and self.auto:
+        if self.instance_norm and precision != "auto" and precision not in ("exact", "split"):
+            try:
+                mk(precision[:-len("_verified")] if precision.endswith("_verified") else precision)
+            except RuntimeError as e:
+                if "adainnorm" not in str(e):
+                    raise
+                raise NotImplementedError(str(e)) from e
+        if (self.wide_vocab or self.instance_norm) and self.auto:
             assert verifier in ("split", "exact")
             self.engine = mk(verifier)
             self.selected_precision = verifier
@@ -317,6 +356,17 @@ class HipMaskAndReplaceDiffusion:
         sel = self.selected_precision
         rep = {"precision_requested": self.precision, "engine_selected": sel,
                "expected_throughput": THROUGHPUT_CLASS.get(sel, "?")}
+        if variant_name(self.pos_emb, self.timestep_type):
+            rep["denoiser_variant"] = variant_name(self.pos_emb, self.timestep_type)
+        if self.auto and self.instance_norm and not self.wide_vocab:
+            rep["reason"] = (f"timestep_type={self.timestep_type}: instance norm over a layout's rows runs on the tiled kernels of the "
+                             "reference-precision engines (split / exact) only; no fp16 engine was built or measured")
+            self.selection_report = rep
+            logger.info("layout_dm_amd: precision='auto' selected engine '%s': timestep_type=%s normalises per (layout, channel) over the "
+                        "sequence axis, which only the reference-precision engines (split / exact) serve — no fp16 engine was built; "
+                        "expect less than %s (its LayerNorm-fed GEMMs run as separate tiled launches)", sel, self.timestep_type,
+                        rep["expected_throughput"])
+            return
         if self.verified is not None:
             explicit = self.precision in ("mixed_verified", "hybrid_verified")
             cal = self._v_fast.calibration if not explicit else {}

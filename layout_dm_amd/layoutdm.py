@@ -20,7 +20,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .diffusion import HipMaskAndReplaceDiffusion, _cfg_get
+from .diffusion import POS_EMBS, HipMaskAndReplaceDiffusion, _cfg_get, check_timestep_type
 
 
 def _find(cfg, key):
@@ -191,8 +191,14 @@ class LayoutDM:
         if q_type not in ("constrained", "vanilla"):  # Q_TYPES, layoutdm.py:20-23
             raise NotImplementedError(f"q_type={q_type}: constrained (LayoutDM default, experiment/layoutdm.yaml:18) "
                                       "or vanilla")
-        if transformer_type != "flattened" or pos_emb != "elem_attr":
-            raise NotImplementedError("only transformer_type=flattened / pos_emb=elem_attr")
+        if transformer_type == "aggregated":
+            raise NotImplementedError(
+                "transformer_type=aggregated: not supported, and the reference cannot instantiate it either — base.py:85-93 calls "
+                "CategoricalAggregatedTransformer with arguments its constructor (nn_lib.py:408-415) does not take")
+        if transformer_type != "flattened":
+            raise NotImplementedError(f"transformer_type={transformer_type}: only flattened")
+        if pos_emb not in POS_EMBS:  # base.py:70-84
+            raise NotImplementedError(f"pos_emb={pos_emb}: elem_attr (LayoutDM default) or default (experiment/vqdiffusion.yaml)")
         assert seq_type in ["set", "poset"]
         # make sure MASK is the last vocabulary (layoutdm.py:46)
         assert tokenizer.id_to_name(tokenizer.N_total - 1) == "mask"
@@ -205,15 +211,14 @@ class LayoutDM:
         n_head = int(_find(backbone_cfg, "nhead"))
         n_layer = int(_find(backbone_cfg, "num_layers"))
         ttype = _find(backbone_cfg, "timestep_type")
-        if ttype != "adalayernorm":
-            raise NotImplementedError(f"timestep_type={ttype}: only adalayernorm (experiment/layoutdm.yaml:13-16)")
+        check_timestep_type(ttype)  # Block, transformer_utils.py:124-156: the *_mlp kinds stay refused
         dstep = int(_find(backbone_cfg, "diffusion_step") or num_timesteps)
         assert dstep == num_timesteps
         inner = HipMaskAndReplaceDiffusion(
             n_category=tokenizer.N_category, n_bin=tokenizer.N_bbox_per_var, max_elem=tokenizer.max_seq_length,
             n_attr=tokenizer.N_var_per_element, d_model=d_model, n_head=n_head, d_ff=d_ff, n_layer=n_layer,
             num_timesteps=num_timesteps, precision=precision, max_batch=max_batch, device=device, q_type=q_type,
-            auxiliary_loss_weight=auxiliary_loss_weight)
+            auxiliary_loss_weight=auxiliary_loss_weight, pos_emb=pos_emb, timestep_type=ttype)
         assert inner.num_classes == tokenizer.N_total and inner.max_token_length == tokenizer.max_token_length
         self.model = _ModuleShim(inner, self)
         self._refine_table = None

@@ -124,8 +124,19 @@ PREFIX = "model.module."  # CustomDataParallel wrapper, models/layoutdm.py:52
 
 
 def synth_state_dict(spec: ModelSpec, seed: int = 0, perturb: bool = False, prefix: str = PREFIX,
-                     weight_std: float = 0.02):
-    """Returns {key: np.ndarray(float32)} with the 100 reference keys."""
+                     weight_std: float = 0.02, pos_emb: str = "elem_attr", timestep_type="adalayernorm"):
+    """Returns {key: np.ndarray(float32)} with the 100 reference keys.
+
+    pos_emb / timestep_type: the denoiser variants of the reference's constructor — exactly the key set and shapes of its
+    state_dict() for that variant (the defaults draw what they always drew):
+      pos_emb="default"                          transformer.pos_emb.pos_emb (S, D) instead of elem_emb / attr_emb (nn_lib.py:73-88)
+      timestep_type "adalayernorm" / "adainnorm"       norm1.emb.weight + norm1.linear.*   (the two share their keys)
+      timestep_type "adalayernorm_abs" / "adainnorm_abs"   norm1.linear.* only: the sinusoid has no parameters (transformer_utils.py:34-49)
+      timestep_type None                         norm1.weight / norm1.bias, a plain nn.LayerNorm (transformer_utils.py:155)"""
+    if pos_emb not in ("elem_attr", "default"):
+        raise ValueError(f"pos_emb={pos_emb}")
+    if timestep_type not in ("adalayernorm", "adainnorm", "adalayernorm_abs", "adainnorm_abs", None):
+        raise ValueError(f"timestep_type={timestep_type}")
     rng = np.random.default_rng(seed)
     D, F, C, T = spec.d_model, spec.d_ff, spec.n_class, spec.n_step
 
@@ -148,8 +159,11 @@ def synth_state_dict(spec: ModelSpec, seed: int = 0, perturb: bool = False, pref
     sd.update(schedule_buffers(spec))
     tr = "transformer."
     sd[tr + "cat_emb.weight"] = normal(C, D)
-    sd[tr + "pos_emb.elem_emb"] = rng.random((spec.max_elem, D)).astype(np.float32)
-    sd[tr + "pos_emb.attr_emb"] = rng.random((spec.n_attr, D)).astype(np.float32)
+    if pos_emb == "default":
+        sd[tr + "pos_emb.pos_emb"] = rng.random((spec.seq_len, D)).astype(np.float32)
+    else:
+        sd[tr + "pos_emb.elem_emb"] = rng.random((spec.max_elem, D)).astype(np.float32)
+        sd[tr + "pos_emb.attr_emb"] = rng.random((spec.n_attr, D)).astype(np.float32)
     for i in range(spec.n_layer):
         b = f"{tr}backbone.layers.{i}."
         sd[b + "self_attn.in_proj_weight"] = normal(3 * D, D)
@@ -160,9 +174,14 @@ def synth_state_dict(spec: ModelSpec, seed: int = 0, perturb: bool = False, pref
         sd[b + "linear1.bias"] = bias(F)
         sd[b + "linear2.weight"] = normal(D, F)
         sd[b + "linear2.bias"] = bias(D)
-        sd[b + "norm1.emb.weight"] = normal(T, D)
-        sd[b + "norm1.linear.weight"] = normal(2 * D, D)
-        sd[b + "norm1.linear.bias"] = bias(2 * D)
+        if timestep_type is None:
+            sd[b + "norm1.weight"] = gamma(D)
+            sd[b + "norm1.bias"] = bias(D)
+        else:
+            if not timestep_type.endswith("_abs"):
+                sd[b + "norm1.emb.weight"] = normal(T, D)
+            sd[b + "norm1.linear.weight"] = normal(2 * D, D)
+            sd[b + "norm1.linear.bias"] = bias(2 * D)
         sd[b + "norm2.weight"] = gamma(D)
         sd[b + "norm2.bias"] = bias(D)
     sd[tr + "head.0.weight"] = gamma(D)
