@@ -261,6 +261,10 @@ int ldm_get_tie_flags(ldm_handle* h, uint8_t* d_flags, int n_steps, int B, void*
  * step-0 table instead of running the denoiser (one-launch loop, all-[MASK] layouts: ldm_describe `step0_cache`).  host_out
  * (n) uint8 on the HOST, n <= max_batch; synchronises the device.  Fails where the handle has no such loop. */
 int ldm_dev_step0_flags(ldm_handle* h, uint8_t* host_out, int n);
+/* Development hook: the handle's cache of captured sampling loops (per-step path, use_graph): *entries = graphs held now (at most 8
+ * keys, the oldest evicted), *captures = keys captured since ldm_create (one count per key, not per lane).  A call that replays a
+ * cached key changes neither.  Touches no device state. */
+int ldm_dev_graph_cache(ldm_handle* h, int* entries, int* captures);
 
 /* ---- cond=relation, split-step form ------------------------------------------------------- */
 /* The logit adjustment alone (`num_update` SGD steps on the mean relational-constraint loss, analytic gradient;

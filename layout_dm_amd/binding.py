@@ -27,7 +27,7 @@ EXPORTS = (
     "ldm_denoise_logits", "ldm_posterior", "ldm_sample_tokens", "ldm_sample_step", "ldm_sample_loop",
     "ldm_decode_layouts", "ldm_relation_update", "ldm_set_tie_report", "ldm_get_tie_flags",
     "ldm_last_loop_ms", "ldm_set_profiling", "ldm_profile_count", "ldm_profile_get", "ldm_profile_reset",
-    "ldm_abi_version", "ldm_get_layout", "ldm_describe", "ldm_dev_step0_flags",
+    "ldm_abi_version", "ldm_get_layout", "ldm_describe", "ldm_dev_step0_flags", "ldm_dev_graph_cache",
     # FID feature extractor (bound in layout_dm_amd/fid.py)
     "ldm_fid_create", "ldm_fid_destroy", "ldm_fid_last_error", "ldm_fid_load_weight", "ldm_fid_finalize",
     "ldm_fid_features", "ldm_prdc", "ldm_layout_metrics",
@@ -139,6 +139,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_set_tie_report.argtypes = [vp, C.c_float, C.c_float]
     lib.ldm_get_tie_flags.argtypes = [vp, vp, i32, i32, vp]
     lib.ldm_dev_step0_flags.argtypes = [vp, vp, i32]
+    lib.ldm_dev_graph_cache.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.ldm_last_loop_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ldm_set_profiling.argtypes = [vp, i32]
     lib.ldm_profile_count.argtypes = [vp]
@@ -572,6 +573,13 @@ class Engine:
         out = np.zeros(int(B), dtype=np.uint8)
         self._check(self.lib.ldm_dev_step0_flags(self._h, out.ctypes.data_as(C.c_void_p), int(B)), "ldm_dev_step0_flags")
         return out
+
+    def graph_cache(self):
+        """Development hook: (entries, captures) of the handle's cache of captured sampling loops — graphs held now (at most 8
+        keys) and keys captured since the engine was created.  A sample_loop call that replays a cached key changes neither."""
+        entries, captures = C.c_int(), C.c_int()
+        self._check(self.lib.ldm_dev_graph_cache(self._h, C.byref(entries), C.byref(captures)), "ldm_dev_graph_cache")
+        return int(entries.value), int(captures.value)
 
     # ------------------------------------------------------------------ cond=relation
     def make_relation(self, graph, centres, canvas_bins, relation_lambda: float, num_update: int, n_graph_total: int):

@@ -155,7 +155,7 @@ extern "C" void ldm_destroy(ldm_handle* h) {
   DeviceGuard guard(h->device);
   (void)hipDeviceSynchronize();
   h->drain_profile();
-  for (auto& g : h->graphs) g.destroy();
+  h->graphs.drop_all();
   for (auto& kv : h->raw)
     if (kv.second.d) (void)hipFree(kv.second.d);
   for (void* p : h->owned) (void)hipFree(p);
@@ -322,8 +322,7 @@ extern "C" int ldm_set_tie_report(ldm_handle* h, float tie_rel, float tie_abs) {
     // captured graphs carry the flag pointers / thresholds of their capture; a replay on another stream may still be
     // executing one of them
     HIP_OK(h, hipDeviceSynchronize());
-    for (auto& g : h->graphs) g.destroy();
-    h->graphs.clear();
+    h->graphs.drop_all();
   }
   h->tie_rel = tie_rel;
   h->tie_abs = tie_abs;

@@ -3,8 +3,8 @@
 // synthetic operands (tests/test_attnout_gpu.py), and one row-resident LayerNorm + GEMM launch of a live handle on the caller's rows
 // (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py), and one fused attention + out_proj (+ FFN) launch of a live handle on the caller's panels
 // (ldm_dev_attnout_run, tests/test_attnout_kernel_gpu.py), and one launch of a LayerNorm / GEMM / attention kernel of the tiled engines on the caller's
-// buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py).  Nothing in the product path calls
-// into this file.
+// buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py), and the counters of the
+// handle's cache of captured loops (ldm_dev_graph_cache, tests/test_loop_graph_cache_gpu.py).  Nothing in the product path calls into this file.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -53,6 +53,15 @@ extern "C" int ldm_dev_step0_flags(ldm_handle* h, uint8_t* host_out, int n) {
   ON_DEVICE(h);
   HIP_OK(h, hipDeviceSynchronize());
   HIP_OK(h, hipMemcpy(host_out, h->step0_flags, (size_t)n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The handle's cache of captured loops (ldm_handle.h GraphCache): entries held now, and entries captured since create — one per key,
+// whatever its lane count.  A hit leaves both as they were (tests/test_loop_graph_cache_gpu.py).
+extern "C" int ldm_dev_graph_cache(ldm_handle* h, int* entries, int* captures) {
+  if (!h || !entries || !captures) return -1;
+  *entries = (int)h->graphs.entries.size();
+  *captures = h->graphs.captures;
   return 0;
 }
 

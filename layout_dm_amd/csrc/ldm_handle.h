@@ -5,6 +5,7 @@
 //   ldm_weights.cpp  checkpoint upload, fp16 / LDS weight images, parameter tables (ldm_load_weight / ldm_finalize_weights)
 //   ldm_denoise.cpp  the launch sequence of one denoiser pass over a chunk, per numerics mode
 //   ldm_vb_api.cpp   scoring given layouts: forward noising draw, variational-bound terms (ldm_q_sample / ldm_vb_terms / ldm_vb_step)
+//   ldm_loop_plan.h  a sampling call's cut into passes and lanes, its graph key, the timestep range rule (host-pure)
 //   ldm_loop.cpp     the hot path: one reverse step, the one-launch loop, the per-lane hipGraph loop (ldm_sample_step / _loop)
 #pragma once
 #include "../../include/ldm_hip.h"
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "ldm_kernels.h"
+#include "ldm_loop_plan.h"
 #include "ldm_pack.h"
 
 using namespace ldm;
@@ -91,29 +93,8 @@ struct PendingEvent {
   hipEvent_t a, b;
 };
 
-struct GraphKey {
-  int B, n_steps, kind, top_k, has_cond, has_strong, has_weak, pad_disable, has_inter;
-  int has_rel = 0, rel_num_update = 0, rel_n_graph = 0, rel_bins[4] = {0, 0, 0, 0};
-  float tie_rel = 0.f, tie_abs = 0.f;
-  float rel_lambda = 0.f;
-  const void* rel_edges = nullptr;
-  float temperature, top_p;
-  const void *tokens, *cond_seq, *strong, *weak;
-  std::vector<int32_t> t_model, t_post;
-  bool operator==(const GraphKey& o) const {
-    return B == o.B && n_steps == o.n_steps && kind == o.kind && top_k == o.top_k && has_cond == o.has_cond &&
-           has_strong == o.has_strong && has_weak == o.has_weak && pad_disable == o.pad_disable &&
-           has_inter == o.has_inter && tie_rel == o.tie_rel && tie_abs == o.tie_abs && has_rel == o.has_rel && rel_num_update == o.rel_num_update &&
-           rel_n_graph == o.rel_n_graph && rel_lambda == o.rel_lambda && rel_edges == o.rel_edges &&
-           rel_bins[0] == o.rel_bins[0] && rel_bins[1] == o.rel_bins[1] && rel_bins[2] == o.rel_bins[2] &&
-           rel_bins[3] == o.rel_bins[3] && temperature == o.temperature && top_p == o.top_p && tokens == o.tokens &&
-           cond_seq == o.cond_seq && strong == o.strong && weak == o.weak &&
-           t_model == o.t_model && t_post == o.t_post;
-  }
-};
-
 struct GraphEntry {
-  GraphKey key;
+  GraphKey key;                       // ldm_loop_plan.h
   std::vector<hipGraph_t> graph;      // one per lane
   std::vector<hipGraphExec_t> exec;
   void destroy() {
@@ -123,6 +104,40 @@ struct GraphEntry {
       if (g) (void)hipGraphDestroy(g);
     exec.clear();
     graph.clear();
+  }
+};
+
+// The captured loops of a handle, oldest first.  The one place that destroys a cached graph; a caller that drops entries a replay may still
+// be executing synchronises the device first (the cache itself never does).
+struct GraphCache {
+  static constexpr size_t kMaxEntries = 8;
+  std::vector<GraphEntry> entries;
+  int captures = 0;   // entries inserted since create, one per key whatever its lane count (ldm_dev_graph_cache)
+  bool empty() const { return entries.empty(); }
+  GraphEntry* find(const GraphKey& key) {
+    for (auto& g : entries)
+      if (g.key == key) return &g;
+    return nullptr;
+  }
+  GraphEntry* insert(const GraphEntry& e) {
+    if (entries.size() >= kMaxEntries) drop(0);   // small LRU-less cache: the oldest goes (no device synchronisation in front of it)
+    entries.push_back(e);
+    ++captures;
+    return &entries.back();
+  }
+  void drop_all() {
+    while (!entries.empty()) drop(entries.size() - 1);
+  }
+  // the relation edge staging at `old` is about to be freed: no graph that recorded its address may be replayed again
+  void drop_where_rel_edges(const void* old) {
+    for (size_t i = entries.size(); i-- > 0;)
+      if (entries[i].key.rel_edges == old) drop(i);
+  }
+
+ private:
+  void drop(size_t i) {
+    entries[i].destroy();
+    entries.erase(entries.begin() + i);
   }
 };
 
@@ -230,7 +245,7 @@ struct ldm_handle {
   std::vector<PendingEvent> pending;
   hipEvent_t loop_a = nullptr, loop_b = nullptr;
   bool loop_timed = false;
-  std::vector<GraphEntry> graphs;
+  GraphCache graphs;
 
   int fail(int code, const char* fmt, ...) {
     char buf[1024];

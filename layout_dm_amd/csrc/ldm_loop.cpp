@@ -62,6 +62,18 @@ int ldm_host::check_live_temperature(ldm_handle* h, const ldm_sampler* s) {
   return 0;
 }
 
+// where ldm_sample_step's and ldm_sample_loop's checks coincide: the stretch in front of their argument checks
+static int check_call(ldm_handle* h, const ldm_sampler* s, int B) {
+  int rc = check_ready(h, B);
+  if (rc) return rc;
+  if ((rc = check_sampler(h, s))) return rc;
+  return check_live_temperature(h, s);
+}
+
+static int check_timestep_range(ldm_handle* h, const int32_t* t_model, const int32_t* t_post, int n) {
+  return check_timesteps(t_model, t_post, n, h->T) ? 0 : h->fail(-1, kTimestepRangeMsg, h->T);
+}
+
 static int check_relation(ldm_handle* h, const ldm_relation* rel, const ldm_cond* cond, int B) {
   if (!rel) return 0;
   if (!cond || !cond->d_cond_seq) return h->fail(-1, "cond=relation needs cond->d_cond_seq (the conditioned sequence)");
@@ -98,13 +110,12 @@ void ldm_host::fill_rel(ldm_handle* h, RelArgs& a, const ldm_relation* rel, size
 
 // one fused reverse step over the whole batch, chunk by chunk through the workspace `ws`.  `cond` / `rel` describe layouts
 // 0..B of THIS call (the loop body hands over pointers already advanced to its chunk); rel_layout_off = position of row 0
-// inside the relation graph's CSR offsets.
+// inside the relation graph's CSR offsets.  The timesteps are the entry point's, already through check_timestep_range; the
+// chunk loop is the workspace's capacity (a pass of the loop body is one chunk at most), not a cut of the call.
 static int step_all(ldm_handle* h, Workspace& ws, const int32_t* tin, int32_t* tout, int t_model, int t_post, const ldm_cond* cond,
                     const ldm_relation* rel, size_t rel_layout_off, const ldm_sampler* s, int step, int B,
                     size_t rng_layout_off, hipStream_t st, bool skip_embed = false, bool embed_next = false,
                     int tie_row = -1) {
-  if (t_model < 0 || t_model >= h->T || t_post < 0 || t_post >= h->T)
-    return h->fail(-1, "timestep out of range [0,%d)", h->T);  // constrained.py:139
   for (int off = 0; off < B; off += h->plan.chunk) {
     const int Bc = std::min(h->plan.chunk, B - off);
     int rc = denoise_chunk(h, ws, tin + (size_t)off * h->plan.S, t_model, Bc, st, skip_embed);
@@ -325,49 +336,33 @@ static int tie_begin(ldm_handle* h, const ldm_sampler* s, const ldm_relation* re
 extern "C" int ldm_sample_step(ldm_handle* h, const int32_t* d_tokens_in, int32_t* d_tokens_out, int t_model,
                                int t_post, const ldm_cond* cond, const ldm_relation* rel, const ldm_sampler* s,
                                uint64_t seed, uint64_t first_layout, int step, int B, void* stream) {
-  int rc = check_ready(h, B);
+  int rc = check_call(h, s, B);
   if (rc) return rc;
-  if ((rc = check_sampler(h, s))) return rc;
-  if ((rc = check_live_temperature(h, s))) return rc;
   if (!d_tokens_in || !d_tokens_out) return h->fail(-1, "null argument");
   ON_DEVICE(h);
   if ((rc = check_relation(h, rel, cond, B))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = set_rng(h, seed, first_layout, st))) return rc;
-  if (t_model < 0 || t_model >= h->T || t_post < 0 || t_post >= h->T)
-    return h->fail(-1, "timestep out of range [0,%d)", h->T);  // constrained.py:139
+  const int32_t tm = t_model, tp = t_post;
+  if ((rc = check_timestep_range(h, &tm, &tp, 1))) return rc;
   if ((rc = tie_begin(h, s, rel, 1, B, st))) return rc;
   if (loop_fusable(h, rel)) {
-    const int32_t tm = t_model, tp = t_post;
     if ((rc = run_loop_fused(h, d_tokens_in, d_tokens_out, cond, rel, &tm, &tp, 1, s, step, B, nullptr, 0, st))) return rc;
-  } else if ((rc = step_all(h, h->ws[0], d_tokens_in, d_tokens_out, t_model, t_post, cond, rel, 0, s, step, B, 0, st, false, false, 0))) {
+  } else if ((rc = step_all(h, h->ws[0], d_tokens_in, d_tokens_out, t_model, t_post, cond, rel, 0, s, step, B, 0, st, false, false, 0)))
     return rc;
-  }
   HIP_OK(h, hipGetLastError());
   return 0;
 }
 
-// The T-step loop of the chunks of ONE lane (lane < 0: every chunk, in order, through lane 0's workspace).
-static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation* rel, const int32_t* t_model,
-                         const int32_t* t_post, int n_steps, const ldm_sampler* s, int B, int32_t* d_inter,
-                         int lane, hipStream_t st) {
-  // state lives in tok_a / tok_b (ping-pong); chunk-major order keeps one chunk's activations and the
-  // weights resident in L2 / Infinity Cache for all T steps before moving to the next chunk
+// The T-step loop of the passes of ONE lane of the cut (lane < 0: every pass, in order, through lane 0's workspace).
+static int run_loop_body(ldm_handle* h, const LoopCut& cut, const ldm_cond* cond, const ldm_relation* rel, const int32_t* t_model,
+                         const int32_t* t_post, int n_steps, const ldm_sampler* s, int32_t* d_inter, int lane, hipStream_t st) {
+  // state lives in tok_a / tok_b (ping-pong); chunk-major order keeps one chunk's activations and the weights resident in L2 / Infinity Cache for all T steps
   const size_t S = h->plan.S;
-  // BALANCED chunks (r06): a call of B layouts needs ceil(B / chunk) passes; they share the layouts evenly — 300 layouts are 150 + 150, not 256 + 44
-  // (the 44-layout pass kept 212 of 256 compute units idle for as long as the full one; a call's two passes also overlap on the lanes when each
-  // fills only part of the chip: same-box split 1 012 -> 1 105, hybrid 1 818 -> 2 011 layouts/s at B = 300; + 6 % / + 1 % at B = 400).  Tokens do not depend on the cut
-  // (B = 300 as 150 + 150: tests/test_hip_parity.py test_split_mode_loop_properties, tests/test_r04_parity.py test_relation_in_the_loop_kernel_equals_the_per_step_path).
-  // Only where the remainder is small: with a remainder of >= 3/4 of a chunk the uneven cut is 2 % FASTER for the short hybrid launches (488 = 256 + 232: 2 142
-  // against 2 093 for 244 + 244 — passes of unequal length drift against each other on the lanes instead of running in lock-step; profiles/r06_call16_17_25_*).
-  const int n_pass = (B + h->plan.chunk - 1) / h->plan.chunk;
-  const int rem = B - (n_pass - 1) * h->plan.chunk;
-  const int cb = (h->plan.balanced_chunks && n_pass > 1 && 4 * rem < 3 * h->plan.chunk) ? (B + n_pass - 1) / n_pass : h->plan.chunk;
-  const int first = lane < 0 ? 0 : lane * cb;
-  const int stride = lane < 0 ? cb : h->plan.n_lanes * cb;
   Workspace& ws = h->ws[lane < 0 ? 0 : lane];
-  for (int off = first; off < B; off += stride) {
-    const int Bc = std::min(cb, B - off);
+  for (int k = 0; k < cut.n_pass; ++k) {
+    if (!cut.owns(lane, k)) continue;
+    const int off = cut.offset(k), Bc = cut.size(k);
     ldm_cond cc{};
     if (cond) {
       cc = *cond;
@@ -375,8 +370,7 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
       if (cc.d_strong_mask) cc.d_strong_mask += off * S;
       if (cc.d_weak_logits) cc.d_weak_logits += (size_t)off * h->plan.C * S;
     }
-    int32_t* cur = h->tok_a + off * S;
-    int32_t* nxt = h->tok_b + off * S;
+    int32_t *cur = h->tok_a + off * S, *nxt = h->tok_b + off * S;
     // the stack kernel takes raw rows and computes its own row statistics, so the posterior kernel of step i can write
     // step i + 1's embedding itself (no separate embedding launch inside the loop)
     const bool fuse_embed = h->plan.structure == Structure::Stack;
@@ -385,8 +379,7 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
                         fuse_embed && i > 0, fuse_embed && i + 1 < n_steps, i);
       if (rc) return rc;
       if (d_inter)
-        HIP_OK(h, hipMemcpyAsync(d_inter + ((size_t)i * B + off) * S, nxt, (size_t)Bc * S * 4,
-                                 hipMemcpyDeviceToDevice, st));
+        HIP_OK(h, hipMemcpyAsync(d_inter + ((size_t)i * cut.B + off) * S, nxt, (size_t)Bc * S * 4, hipMemcpyDeviceToDevice, st));
       std::swap(cur, nxt);
     }
     if (n_steps % 2 == 1)  // result sits in tok_b: bring it back to tok_a
@@ -395,18 +388,154 @@ static int run_loop_body(ldm_handle* h, const ldm_cond* cond, const ldm_relation
   return 0;
 }
 
+// ---- the per-lane hipGraph loop, step by step
+// A captured graph only ever sees fixed addresses: the caller's constraints are copied into handle-owned staging buffers, so
+// the graph is reused across batches whose cond tensors live elsewhere.  *staged describes the copies.
+static int stage_cond(ldm_handle* h, const ldm_cond* cond, int B, hipStream_t st, ldm_cond* staged) {
+  const size_t nS = (size_t)B * h->plan.S;
+  staged->pad_disable = cond->pad_disable;
+  if (cond->d_cond_seq) {
+    HIP_OK(h, hipMemcpyAsync(h->st_cond_seq, cond->d_cond_seq, nS * 4, hipMemcpyDeviceToDevice, st));
+    staged->d_cond_seq = h->st_cond_seq;
+  }
+  if (cond->d_strong_mask) {
+    HIP_OK(h, hipMemcpyAsync(h->st_strong, cond->d_strong_mask, nS, hipMemcpyDeviceToDevice, st));
+    staged->d_strong_mask = h->st_strong;
+  }
+  if (cond->d_weak_logits) {
+    int rc = 0;
+    if (!h->st_weak && (rc = h->dalloc(&h->st_weak, (size_t)h->cfg.max_batch * h->plan.C * h->plan.S, false))) return rc;
+    HIP_OK(h, hipMemcpyAsync(h->st_weak, cond->d_weak_logits, nS * h->plan.C * 4, hipMemcpyDeviceToDevice, st));
+    staged->d_weak_logits = h->st_weak;
+  }
+  return 0;
+}
+
+// Room for n_edges edges in the relation edge staging.  A grown buffer has a new address: graphs keyed on the old one can never
+// hit again — drop them and release the old buffer, once NOTHING on the device can still be reading it (an earlier replay may
+// run on another stream than the one the caller synchronised).
+static int grow_rel_edges(ldm_handle* h, size_t n_edges) {
+  if (n_edges <= h->st_rel_cap) return 0;
+  int32_t* old = h->st_rel_edges;
+  if (old) HIP_OK(h, hipDeviceSynchronize());
+  const size_t cap = std::max<size_t>(1024, n_edges * 2);
+  int rc = h->dalloc(&h->st_rel_edges, 3 * cap);
+  if (rc) return rc;
+  h->st_rel_cap = cap;
+  if (old) {
+    h->graphs.drop_where_rel_edges(old);
+    h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), (void*)old), h->owned.end());
+    (void)hipFree(old);
+  }
+  return 0;
+}
+
+// ... and the relation graph: CSR offsets are read back once (host) to size the edge staging
+static int stage_relation(ldm_handle* h, const ldm_relation* rel, int B, hipStream_t st, ldm_relation* staged) {
+  int rc = 0;
+  *staged = *rel;
+  std::vector<int32_t> off(B + 1);
+  HIP_OK(h, hipMemcpyAsync(off.data(), rel->d_edge_offsets, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIP_OK(h, hipStreamSynchronize(st));
+  const int32_t e0 = off[0], ne = off[B] - off[0];
+  if (ne < 0) return h->fail(-1, "ldm_relation: edge offsets are not monotonic");
+  if (!h->st_rel_off && (rc = h->dalloc(&h->st_rel_off, (size_t)h->cfg.max_batch + 1))) return rc;
+  if (!h->st_rel_centres && (rc = h->dalloc(&h->st_rel_centres, (size_t)4 * h->cfg.n_bin))) return rc;
+  if ((rc = grow_rel_edges(h, (size_t)ne))) return rc;
+  for (auto& o : off) o -= e0;
+  HIP_OK(h, hipMemcpyAsync(h->st_rel_off, off.data(), (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
+  HIP_OK(h, hipStreamSynchronize(st));  // `off` is pageable host memory
+  const size_t cap = h->st_rel_cap;
+  if (ne > 0) {
+    HIP_OK(h, hipMemcpyAsync(h->st_rel_edges, rel->d_edge_src + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->st_rel_edges + cap, rel->d_edge_dst + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
+    HIP_OK(h, hipMemcpyAsync(h->st_rel_edges + 2 * cap, rel->d_edge_attr + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
+  }
+  HIP_OK(h, hipMemcpyAsync(h->st_rel_centres, rel->d_centres, (size_t)4 * h->cfg.n_bin * 4, hipMemcpyDeviceToDevice, st));
+  staged->d_edge_offsets = h->st_rel_off;
+  staged->d_edge_src = h->st_rel_edges;
+  staged->d_edge_dst = h->st_rel_edges + cap;
+  staged->d_edge_attr = h->st_rel_edges + 2 * cap;
+  staged->d_centres = h->st_rel_centres;
+  return 0;
+}
+
+// intermediates are captured into a handle-owned buffer (fixed address) and copied out after the launch, so
+// get_intermediate_results=True replays the same graph instead of re-capturing for every caller pointer
+static int stage_intermediates(ldm_handle* h, int n_steps, int32_t** inter_dst) {
+  if (n_steps > h->T) return h->fail(-1, "intermediates: n_steps %d > T %d", n_steps, h->T);
+  int rc = 0;
+  if (!h->st_inter && (rc = h->dalloc(&h->st_inter, (size_t)h->T * h->cfg.max_batch * h->plan.S, false))) return rc;
+  *inter_dst = h->st_inter;
+  return 0;
+}
+
+// One linear graph per lane of the cut into *entry, each captured on a private stream so that the caller's stream state is
+// untouched.  Whatever ends the function early, the guard ends an open capture (discarding its graph), destroys the private
+// stream and destroys the graphs *entry holds so far: nothing between begin and end of a capture returns past it.
+static int capture_lanes(ldm_handle* h, const LoopCut& cut, const GraphKey& key, const ldm_cond* cond, const ldm_relation* rel,
+                         const int32_t* t_model, const int32_t* t_post, int n_steps, const ldm_sampler* s, int32_t* inter_dst,
+                         GraphEntry* entry) {
+  struct Guard {
+    GraphEntry* entry;
+    hipStream_t cap = nullptr;
+    bool capturing = false, done = false;
+    hipError_t end_capture(hipGraph_t* graph) {   // ... and the private stream with it
+      const hipError_t e = capturing ? hipStreamEndCapture(cap, graph) : hipSuccess;
+      capturing = false;
+      if (cap) (void)hipStreamDestroy(cap);
+      cap = nullptr;
+      return e;
+    }
+    ~Guard() {
+      hipGraph_t graph = nullptr;
+      (void)end_capture(&graph);
+      if (graph) (void)hipGraphDestroy(graph);
+      if (!done) entry->destroy();
+    }
+  } guard{entry};
+  entry->key = key;
+  for (int lane = 0; lane < cut.lanes; ++lane) {
+    HIP_OK(h, hipStreamCreateWithFlags(&guard.cap, hipStreamNonBlocking));
+    HIP_OK(h, hipStreamBeginCapture(guard.cap, hipStreamCaptureModeThreadLocal));
+    guard.capturing = true;
+    if (lane > 0 && h->plan.lane_offset_us > 0) launch_delay_us(lane * h->plan.lane_offset_us, guard.cap);
+    const int rc = run_loop_body(h, cut, cond, rel, t_model, t_post, n_steps, s, inter_dst, cut.lanes > 1 ? lane : -1, guard.cap);
+    hipGraph_t graph = nullptr;
+    hipError_t e = guard.end_capture(&graph);
+    if (graph) entry->graph.push_back(graph);   // the entry's from here on
+    if (rc) return rc;
+    if (e != hipSuccess) return h->fail(-2, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
+    hipGraphExec_t exec = nullptr;
+    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) return h->fail(-2, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
+    entry->exec.push_back(exec);
+  }
+  guard.done = true;
+  return 0;
+}
+
+// lane 0 replays on the caller's stream, the others on their own streams between a fork and a join event
+static int replay(ldm_handle* h, const GraphEntry& ge, hipStream_t st) {
+  if (ge.exec.size() > 1) HIP_OK(h, hipEventRecord(h->fork_ev, st));
+  for (size_t lane = 1; lane < ge.exec.size(); ++lane) {
+    HIP_OK(h, hipStreamWaitEvent(h->lane_stream[lane], h->fork_ev, 0));
+    HIP_OK(h, hipGraphLaunch(ge.exec[lane], h->lane_stream[lane]));
+    HIP_OK(h, hipEventRecord(h->lane_done[lane], h->lane_stream[lane]));
+  }
+  HIP_OK(h, hipGraphLaunch(ge.exec[0], st));
+  for (size_t lane = 1; lane < ge.exec.size(); ++lane) HIP_OK(h, hipStreamWaitEvent(st, h->lane_done[lane], 0));
+  return 0;
+}
+
 extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm_cond* cond, const ldm_relation* rel,
                                const int32_t* h_t_model, const int32_t* h_t_post, int n_steps, const ldm_sampler* s,
                                uint64_t seed, uint64_t first_layout, int B, int32_t* d_intermediates, int use_graph,
                                void* stream) {
-  int rc = check_ready(h, B);
+  int rc = check_call(h, s, B);
   if (rc) return rc;
-  if ((rc = check_sampler(h, s))) return rc;
-  if ((rc = check_live_temperature(h, s))) return rc;
   if (!d_tokens_inout || !h_t_model || !h_t_post || n_steps < 1) return h->fail(-1, "bad argument");
-  for (int i = 0; i < n_steps; ++i)
-    if (h_t_model[i] < 0 || h_t_model[i] >= h->T || h_t_post[i] < 0 || h_t_post[i] >= h->T)
-      return h->fail(-1, "timestep out of range [0,%d)", h->T);
+  if ((rc = check_timestep_range(h, h_t_model, h_t_post, n_steps))) return rc;
   ON_DEVICE(h);
   if ((rc = check_relation(h, rel, cond, B))) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -416,172 +545,36 @@ extern "C" int ldm_sample_loop(ldm_handle* h, int32_t* d_tokens_inout, const ldm
   if ((rc = tie_begin(h, s, rel, n_steps, B, st))) return rc;
   if (loop_fusable(h, rel)) {
     // one launch: every layout's workgroup runs all its steps in place on the caller's tokens (no staging, no graph)
-    if ((rc = run_loop_fused(h, d_tokens_inout, d_tokens_inout, cond, rel, h_t_model, h_t_post, n_steps, s, 0, B,
-                             d_intermediates, 0, st, true)))
-      return rc;
-    HIP_OK(h, hipEventRecord(h->loop_b, st));
-    h->loop_timed = true;
-    HIP_OK(h, hipGetLastError());
-    return 0;
-  }
-  HIP_OK(h, hipMemcpyAsync(h->tok_a, d_tokens_inout, nbytes, hipMemcpyDeviceToDevice, st));
-  if (use_graph && !h->profiling) {
-    // copy the constraints into handle-owned staging buffers: the captured graph then only ever sees
-    // fixed addresses and is reused across batches whose cond tensors live elsewhere
-    ldm_cond staged{};
-    if (cond) {
-      const size_t nS = (size_t)B * h->plan.S;
-      staged.pad_disable = cond->pad_disable;
-      if (cond->d_cond_seq) {
-        HIP_OK(h, hipMemcpyAsync(h->st_cond_seq, cond->d_cond_seq, nS * 4, hipMemcpyDeviceToDevice, st));
-        staged.d_cond_seq = h->st_cond_seq;
-      }
-      if (cond->d_strong_mask) {
-        HIP_OK(h, hipMemcpyAsync(h->st_strong, cond->d_strong_mask, nS, hipMemcpyDeviceToDevice, st));
-        staged.d_strong_mask = h->st_strong;
-      }
-      if (cond->d_weak_logits) {
-        if (!h->st_weak && (rc = h->dalloc(&h->st_weak, (size_t)h->cfg.max_batch * h->plan.C * h->plan.S, false))) return rc;
-        HIP_OK(h, hipMemcpyAsync(h->st_weak, cond->d_weak_logits, nS * h->plan.C * 4, hipMemcpyDeviceToDevice, st));
-        staged.d_weak_logits = h->st_weak;
-      }
-      cond = &staged;
-    }
-    // same for the relation graph: CSR offsets are read back once (host) to size the edge staging
-    ldm_relation staged_rel{};
-    if (rel) {
-      staged_rel = *rel;
-      std::vector<int32_t> off(B + 1);
-      HIP_OK(h, hipMemcpyAsync(off.data(), rel->d_edge_offsets, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, st));
-      HIP_OK(h, hipStreamSynchronize(st));
-      const int32_t e0 = off[0], ne = off[B] - off[0];
-      if (ne < 0) return h->fail(-1, "ldm_relation: edge offsets are not monotonic");
-      if (!h->st_rel_off && (rc = h->dalloc(&h->st_rel_off, (size_t)h->cfg.max_batch + 1))) return rc;
-      if (!h->st_rel_centres && (rc = h->dalloc(&h->st_rel_centres, (size_t)4 * h->cfg.n_bin))) return rc;
-      if ((size_t)ne > h->st_rel_cap) {
-        // a grown buffer has a new address: graphs keyed on the old one can never hit again — drop them and release
-        // the old staging buffer, once NOTHING on the device can still be reading it (an earlier replay may run on
-        // another stream than the one synchronised above)
-        int32_t* old = h->st_rel_edges;
-        if (old) HIP_OK(h, hipDeviceSynchronize());
-        const size_t cap = std::max<size_t>(1024, (size_t)ne * 2);
-        if ((rc = h->dalloc(&h->st_rel_edges, 3 * cap))) return rc;
-        h->st_rel_cap = cap;
-        if (old) {
-          for (size_t gi = h->graphs.size(); gi-- > 0;)
-            if (h->graphs[gi].key.rel_edges == old) {
-              h->graphs[gi].destroy();
-              h->graphs.erase(h->graphs.begin() + gi);
-            }
-          h->owned.erase(std::remove(h->owned.begin(), h->owned.end(), (void*)old), h->owned.end());
-          (void)hipFree(old);
-        }
-      }
-      for (auto& o : off) o -= e0;
-      HIP_OK(h, hipMemcpyAsync(h->st_rel_off, off.data(), (size_t)(B + 1) * 4, hipMemcpyHostToDevice, st));
-      HIP_OK(h, hipStreamSynchronize(st));  // `off` is pageable host memory
-      if (ne > 0) {
-        const size_t cap = h->st_rel_cap;
-        HIP_OK(h, hipMemcpyAsync(h->st_rel_edges, rel->d_edge_src + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(h->st_rel_edges + cap, rel->d_edge_dst + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
-        HIP_OK(h, hipMemcpyAsync(h->st_rel_edges + 2 * cap, rel->d_edge_attr + e0, (size_t)ne * 4, hipMemcpyDeviceToDevice, st));
-      }
-      HIP_OK(h, hipMemcpyAsync(h->st_rel_centres, rel->d_centres, (size_t)4 * h->cfg.n_bin * 4, hipMemcpyDeviceToDevice, st));
-      staged_rel.d_edge_offsets = h->st_rel_off;
-      staged_rel.d_edge_src = h->st_rel_edges;
-      staged_rel.d_edge_dst = h->st_rel_edges + h->st_rel_cap;
-      staged_rel.d_edge_attr = h->st_rel_edges + 2 * h->st_rel_cap;
-      staged_rel.d_centres = h->st_rel_centres;
-      rel = &staged_rel;
-    }
-    GraphKey key{};
-    key.B = B; key.n_steps = n_steps; key.kind = s->kind; key.top_k = s->top_k;
-    key.temperature = s->temperature; key.top_p = s->top_p;
-    key.has_cond = cond != nullptr;
-    key.cond_seq = cond ? cond->d_cond_seq : nullptr;
-    key.strong = cond ? cond->d_strong_mask : nullptr;
-    key.weak = cond ? cond->d_weak_logits : nullptr;
-    key.pad_disable = cond ? cond->pad_disable : 0;
-    // intermediates are captured into a handle-owned buffer (fixed address) and copied out after the launch, so
-    // get_intermediate_results=True replays the same graph instead of re-capturing for every caller pointer
-    int32_t* inter_dst = nullptr;
-    if (d_intermediates) {
-      if (n_steps > h->T) return h->fail(-1, "intermediates: n_steps %d > T %d", n_steps, h->T);
-      if (!h->st_inter && (rc = h->dalloc(&h->st_inter, (size_t)h->T * h->cfg.max_batch * h->plan.S, false))) return rc;
-      inter_dst = h->st_inter;
-    }
-    key.has_inter = inter_dst != nullptr;
-    key.tie_rel = (h->tie_flags && s->kind == LDM_SAMPLE_DETERMINISTIC) ? h->tie_rel : 0.f;
-    key.tie_abs = (h->tie_flags && s->kind == LDM_SAMPLE_DETERMINISTIC) ? h->tie_abs : 0.f;
-    if (rel) {
-      key.has_rel = 1;
-      key.rel_num_update = rel->num_update;
-      key.rel_n_graph = rel->n_graph_total;
-      key.rel_lambda = rel->relation_lambda;
-      key.rel_edges = rel->d_edge_src;
-      for (int x = 0; x < 4; ++x) key.rel_bins[x] = rel->canvas_bins[x];
-    }
-    key.t_model.assign(h_t_model, h_t_model + n_steps);
-    key.t_post.assign(h_t_post, h_t_post + n_steps);
-    GraphEntry* ge = nullptr;
-    for (auto& g : h->graphs)
-      if (g.key == key) ge = &g;
-    // lanes that actually own a chunk of this call
-    const int n_chunks = (B + h->plan.chunk - 1) / h->plan.chunk;
-    const int lanes = std::min(h->plan.n_lanes, n_chunks);
-    if (!ge) {
-      if (h->graphs.size() >= 8) {  // small LRU-less cache: drop the oldest
-        h->graphs[0].destroy();
-        h->graphs.erase(h->graphs.begin());
-      }
-      GraphEntry ne;
-      ne.key = key;
-      for (int lane = 0; lane < lanes; ++lane) {
-        // capture on a private stream so the caller's stream state is untouched; one linear graph per lane
-        hipStream_t cap = nullptr;
-        HIP_OK(h, hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-        HIP_OK(h, hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-        if (lane > 0 && h->plan.lane_offset_us > 0) launch_delay_us(lane * h->plan.lane_offset_us, cap);
-        rc = run_loop_body(h, cond, rel, h_t_model, h_t_post, n_steps, s, B, inter_dst, lanes > 1 ? lane : -1, cap);
-        hipGraph_t graph = nullptr;
-        hipError_t e = hipStreamEndCapture(cap, &graph);
-        (void)hipStreamDestroy(cap);
-        if (rc || e != hipSuccess) {
-          if (graph) (void)hipGraphDestroy(graph);
-          ne.destroy();
-          if (rc) return rc;
-          return h->fail(-2, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        }
-        hipGraphExec_t exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        ne.graph.push_back(graph);
-        if (e != hipSuccess) {
-          ne.destroy();
-          return h->fail(-2, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
-        }
-        ne.exec.push_back(exec);
-      }
-      h->graphs.push_back(ne);
-      ge = &h->graphs.back();
-    }
-    // lane 0 replays on the caller's stream, the others on their own streams between a fork and a join event
-    if (ge->exec.size() > 1) HIP_OK(h, hipEventRecord(h->fork_ev, st));
-    for (size_t lane = 1; lane < ge->exec.size(); ++lane) {
-      HIP_OK(h, hipStreamWaitEvent(h->lane_stream[lane], h->fork_ev, 0));
-      HIP_OK(h, hipGraphLaunch(ge->exec[lane], h->lane_stream[lane]));
-      HIP_OK(h, hipEventRecord(h->lane_done[lane], h->lane_stream[lane]));
-    }
-    HIP_OK(h, hipGraphLaunch(ge->exec[0], st));
-    for (size_t lane = 1; lane < ge->exec.size(); ++lane) HIP_OK(h, hipStreamWaitEvent(st, h->lane_done[lane], 0));
-    if (inter_dst)
-      HIP_OK(h, hipMemcpyAsync(d_intermediates, inter_dst, (size_t)n_steps * B * h->plan.S * 4, hipMemcpyDeviceToDevice, st));
+    if ((rc = run_loop_fused(h, d_tokens_inout, d_tokens_inout, cond, rel, h_t_model, h_t_post, n_steps, s, 0, B, d_intermediates, 0, st, true))) return rc;
   } else {
-    if ((rc = run_loop_body(h, cond, rel, h_t_model, h_t_post, n_steps, s, B, d_intermediates, -1, st))) return rc;
+    const LoopCut cut = cut_call(B, h->plan.chunk, h->plan.n_lanes, h->plan.balanced_chunks);
+    HIP_OK(h, hipMemcpyAsync(h->tok_a, d_tokens_inout, nbytes, hipMemcpyDeviceToDevice, st));
+    if (use_graph && !h->profiling) {
+      ldm_cond staged{};
+      ldm_relation staged_rel{};
+      int32_t* inter_dst = nullptr;
+      if (cond && (rc = stage_cond(h, cond, B, st, &staged))) return rc;
+      if (rel && (rc = stage_relation(h, rel, B, st, &staged_rel))) return rc;
+      if (d_intermediates && (rc = stage_intermediates(h, n_steps, &inter_dst))) return rc;
+      if (cond) cond = &staged;
+      if (rel) rel = &staged_rel;
+      const GraphKey key = graph_key(B, n_steps, *s, cond, inter_dst != nullptr, h->tie_flags != nullptr, h->tie_rel, h->tie_abs, rel,
+                                     h_t_model, h_t_post);
+      const GraphEntry* ge = h->graphs.find(key);
+      if (!ge) {
+        GraphEntry captured;
+        if ((rc = capture_lanes(h, cut, key, cond, rel, h_t_model, h_t_post, n_steps, s, inter_dst, &captured))) return rc;
+        ge = h->graphs.insert(captured);
+      }
+      if ((rc = replay(h, *ge, st))) return rc;
+      if (inter_dst)
+        HIP_OK(h, hipMemcpyAsync(d_intermediates, inter_dst, (size_t)n_steps * B * h->plan.S * 4, hipMemcpyDeviceToDevice, st));
+    } else if ((rc = run_loop_body(h, cut, cond, rel, h_t_model, h_t_post, n_steps, s, d_intermediates, -1, st)))
+      return rc;
+    HIP_OK(h, hipMemcpyAsync(d_tokens_inout, h->tok_a, nbytes, hipMemcpyDeviceToDevice, st));
   }
-  HIP_OK(h, hipMemcpyAsync(d_tokens_inout, h->tok_a, nbytes, hipMemcpyDeviceToDevice, st));
   HIP_OK(h, hipEventRecord(h->loop_b, st));
   h->loop_timed = true;
   HIP_OK(h, hipGetLastError());
   return 0;
 }
-

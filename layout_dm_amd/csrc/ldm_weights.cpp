@@ -371,8 +371,7 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
   // then collect the new allocations in h->derived
   HIP_OK(h, hipDeviceSynchronize());
   h->finalized = false;   // (a finalize that fails part-way must not leave an earlier success standing over freed images)
-  for (auto& g : h->graphs) g.destroy();
-  h->graphs.clear();
+  h->graphs.drop_all();
   h->step0.clear();  // the step-0 logits tables of the loop kernel belong to the weights that are being replaced
   for (void* p : h->derived) (void)hipFree(p);
   h->derived.clear();
@@ -506,8 +505,7 @@ extern "C" int ldm_finalize_weights(ldm_handle* h) {
   HIP_OK(h, hipDeviceSynchronize());
   HIP_OK(h, hipGetLastError());
   // graphs captured against older weights stay valid (pointers unchanged) but drop them anyway
-  for (auto& g : h->graphs) g.destroy();
-  h->graphs.clear();
+  h->graphs.drop_all();
   h->finalized = true;
   return 0;
 }
