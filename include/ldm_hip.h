@@ -243,6 +243,20 @@ int ldm_vb_terms_t(ldm_handle* h, const float* d_logits, const int32_t* d_x0, co
 int ldm_vb_step_t(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, const uint64_t* h_layout,
                   uint64_t seed, uint64_t first_layout, int B, double* d_sums, void* stream);
 
+/* ---- the training loss's gradient with respect to the logits it is computed from (additive export, ABI 5) ------------
+ * d/dlogits of  sum_b  coef[b][0] * (t_b == 0 ? nll_b : kl_b) + coef[b][1] * (t_b == 0 ? nll_b : aux_b)   (token SUMS, as d_sums
+ * reports them; the 1/S, 1/pt, 1/B, the auxiliary weight and the upstream gradient are folded into coef by the caller:
+ * constrained.py:299-330).  h_t: HOST array of B timesteps as in ldm_vb_terms_t.  d_coef (B,2) float64 on the device (a coefficient
+ * rounded to float32 moves the gradient further from the reference's float64 one than the reference's own float32 autograd is);
+ * may be NULL when d_grad is.  d_grad (B,S,C) float32 or NULL (values only): every element is written, the [MASK] column and the
+ * rows of refused tokens as 0.  d_sums (B,4) float64 or NULL, with the bits ldm_vb_terms_t gives on an LDM_PREC_EXACT_F32 handle.
+ * Always the reference-precision (float64) log-softmax, whatever the handle's numerics mode: the logits are the caller's.  Runs no
+ * denoiser; works on every handle, wide vocabularies and per_layout_t=0 included.  No floating-point atomics: two calls give the
+ * same bits, and a layout's rows do not depend on the batch around it.  Return codes as ldm_vb_terms_t: -1 for a t out of range,
+ * -6 for refused tokens. */
+int ldm_vb_grad(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, int B,
+                const double* d_coef, float* d_grad, double* d_sums, void* stream);
+
 /* ---- near-tie report of deterministic decoding (ABI 4; tie_abs: ABI 5) ------------------------
  * north star: "token indices bit-exact under greedy/argmax decoding".  LDM_PREC_FAST_F16's logits carry an error that
  * depends on the checkpoint (3e-4 of max |logit| on the reference's init, 1e-3 on wider weights, more once attention rows

@@ -48,6 +48,8 @@ EXPORTS = (
     "ldm_q_sample", "ldm_vb_terms", "ldm_vb_step",
     # ... at a timestep per layout (Engine.denoise_logits_t / q_sample_t / vb_terms_t / vb_step_t)
     "ldm_denoise_logits_t", "ldm_q_sample_t", "ldm_vb_terms_t", "ldm_vb_step_t",
+    # the training loss's gradient with respect to the logits (Engine.vb_grad; layout_dm_amd/training.py)
+    "ldm_vb_grad",
 )
 
 
@@ -175,6 +177,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.ldm_q_sample_t.argtypes = [vp, vp, vp, vp, u64, u64, i32, vp, vp]
     lib.ldm_vb_terms_t.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     lib.ldm_vb_step_t.argtypes = [vp, vp, vp, vp, vp, u64, u64, i32, vp, vp]
+    lib.ldm_vb_grad.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in EXPORTS:
         if name not in ("ldm_destroy", "ldm_last_error") and not name.startswith("ldm_fid_"):
             getattr(lib, name).restype = C.c_int
@@ -509,6 +512,27 @@ class Engine:
                                                   int(seed), int(first_layout), B, out.data_ptr(), _stream_ptr(self.device)),
                            "ldm_vb_step_t")
         return out
+
+    def vb_grad(self, logits: torch.Tensor, x0: torch.Tensor, xt: torch.Tensor, t, coef, want_grad: bool = True):
+        """(grad | None, sums): d/dlogits (B,S,C) float32 of sum_b coef[b,0] (t_b == 0 ? nll_b : kl_b) + coef[b,1] (t_b == 0 ? nll_b :
+        aux_b) over the token sums (include/ldm_hip.h ldm_vb_grad; coef (B,2) float64: training.loss_coefficients), and the (B,4)
+        float64 sums with vb_terms_t's bits on an exact handle.  t (B,) per-layout timesteps.  want_grad=False: the sums alone
+        (coef may be None).  Runs no denoiser; every handle takes it."""
+        x0, xt = self._tok(x0), self._tok(xt)
+        B = x0.shape[0]
+        assert xt.shape == x0.shape == (B, self.S) and tuple(logits.shape) == (B, self.S, self.C)
+        ht = self._host_t(t, B)
+        logits = logits.to(device=self.device, dtype=torch.float32).contiguous()
+        sums = torch.empty((B, 4), dtype=torch.float64, device=self.device)
+        grad = None
+        if want_grad:
+            coef = torch.as_tensor(coef).to(device=self.device, dtype=torch.float64).contiguous()
+            assert tuple(coef.shape) == (B, 2)
+            grad = torch.empty((B, self.S, self.C), dtype=torch.float32, device=self.device)
+        self._check_tokens(self.lib.ldm_vb_grad(self._h, logits.data_ptr(), x0.data_ptr(), xt.data_ptr(), ht.ctypes.data_as(C.c_void_p), B,
+                                                coef.data_ptr() if want_grad else None, grad.data_ptr() if want_grad else None,
+                                                sums.data_ptr(), _stream_ptr(self.device)), "ldm_vb_grad")
+        return grad, sums
 
     # ------------------------------------------------------------------ hot path
     def sample_step(self, tokens: torch.Tensor, t_model: int, sampling_cfg, t_post: Optional[int] = None,

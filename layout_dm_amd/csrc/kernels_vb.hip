@@ -10,6 +10,7 @@
 //                The group's lane 0 leaves the token's kl / nll / aux / hit in LDS; after one barrier four lanes add a
 //                quantity each over the positions, left to right, in float64.  No floating-point atomics: two runs give
 //                the same bits, and a layout's sums do not depend on the batch around it.
+//   vb_grad_k    the same walk; a token's lane group also writes the token's row of d loss / d logits (ldm_vb_grad)
 // Per-layout timesteps (VbArgs.t_rows / layout_rows, the ldm_*_t entry points): the schedule rows and the Philox key take the
 // layout's own t and layout index (ldm_vb_core.h row_t / row_layout); nullptr: the call's single t and the row position.
 #include "ldm_kernels.h"
@@ -103,6 +104,59 @@ __global__ __launch_bounds__(256) void vb_terms_k(VbArgs p) {
   }
 }
 
+// The training loss's gradient with respect to the logits (ldm_vb_grad; arithmetic: ldm_vb_core.h token_grad), in the lane-group
+// forms of vb_terms_k and always with the float64 log-softmax.  A token's row of p.grad is written by its own lane group, every
+// element once (a refused token: zeros), consecutive lanes consecutive classes: no atomics, two runs give the same bits, and a
+// layout's rows do not depend on the batch around it.  The sums are vb_terms_k<.., FAST = false>'s, bit for bit: the terms come
+// from the same token_terms<true> call.  p.grad == nullptr: that call alone.
+template <int NL, bool LIVE, int CMAX = 192>
+__global__ __launch_bounds__(256) void vb_grad_k(VbArgs p) {
+  constexpr int GPB = 256 / NL;
+  constexpr int NJ = LIVE ? 3 : CMAX / NL;
+  static_assert(CMAX == 192 || (CMAX == 576 && NL == 64), "wide vocabularies: one wavefront per token");
+  static_assert(LIVE || NL == 64, "full-vocabulary map: one wavefront per token");
+  extern __shared__ float sh[];           // [kNumSums][S]
+  const int b = blockIdx.x;
+  const int S = p.S;
+  const int t_b = ldm_vb::row_t(p.t_rows, p.t, b);   // (uniform: one workgroup per layout)
+  const double c_kl = p.grad ? p.coef[2 * b] : 0.0, c_aux = p.grad ? p.coef[2 * b + 1] : 0.0;
+  const int grp = threadIdx.x / NL;
+  const ldm_post::DppGroup<NL, false> g{(int)threadIdx.x % NL};
+  const ldm_post::SlotMap<NL, NJ, LIVE> m{(int)threadIdx.x % NL};
+  for (int s = grp; s < S; s += GPB) {    // (whole groups — DPP rows / wavefronts — enter and leave together)
+    const int row = b * S + s;
+    const int attr = s % p.v.n_attr;
+    ldm_post::TokenArgs a = position_args(p.v, attr);
+    const int x0 = p.x0[row];
+    a.tok = p.xt[row];
+    a.logits = p.logits + (size_t)row * p.ldl;
+    float* grad_row = p.grad ? p.grad + (size_t)row * p.v.n_class : nullptr;
+    ldm_vb::Terms t{0.f, 0.f, 0.f, 0};
+    const int e = ldm_vb::token_error(a, x0, true, a.tok);
+    if (e) {
+      if (g.lane() == 0) atomicOr(p.err, e);
+      if (grad_row)
+        for (int c = g.lane(); c < p.v.n_class; c += NL) grad_row[c] = 0.0f;
+    } else {
+      const ldm_post::StepSchedule sc = ldm_vb::step_schedule(p.sched, p.v.n_attr, attr, p.T, t_b);
+      t = grad_row ? ldm_vb::token_grad(g, m, a, x0, sc, c_kl, c_aux, t_b == 0, grad_row) : ldm_vb::token_terms<true>(g, m, a, x0, sc);
+    }
+    if (g.lane() == 0) {
+      sh[ldm_vb::kSumKl * S + s] = t.kl;
+      sh[ldm_vb::kSumNll * S + s] = t.nll;
+      sh[ldm_vb::kSumAux * S + s] = t.aux;
+      sh[ldm_vb::kSumHit * S + s] = (float)t.hit;
+    }
+  }
+  if (!p.sums) return;                     // (uniform)
+  __syncthreads();
+  if (threadIdx.x < ldm_vb::kNumSums) {
+    double acc = 0.0;
+    for (int s = 0; s < S; ++s) acc += (double)sh[threadIdx.x * S + s];
+    p.sums[(size_t)b * ldm_vb::kNumSums + threadIdx.x] = acc;
+  }
+}
+
 void launch_q_sample(const VbArgs& p, hipStream_t st) {
   const int M = p.B * p.S;
   hipLaunchKernelGGL(q_sample_k, dim3((M + 255) / 256), dim3(256), 0, st, p);
@@ -120,6 +174,15 @@ void launch_vb_terms(const VbArgs& p, hipStream_t st) {
   const bool wave = live_max > 48;
   auto kern = wave ? (p.f32_lse ? vb_terms_k<64, false, true> : vb_terms_k<64, false, false>)
                    : (p.f32_lse ? vb_terms_k<16, true, true> : vb_terms_k<16, true, false>);
+  hipLaunchKernelGGL(kern, dim3(p.B), dim3(256), lds, st, p);
+}
+
+void launch_vb_grad(const VbArgs& p, hipStream_t st) {   // the forms of launch_vb_terms at the float64 log-softmax
+  int live_max = 0;
+  for (int a = 0; a < p.v.n_attr; ++a) live_max = live_max > p.v.count[a] + 2 ? live_max : p.v.count[a] + 2;
+  const size_t lds = (size_t)ldm_vb::kNumSums * p.S * sizeof(float);
+  auto kern = p.v.n_class > 192 ? (live_max > 192 ? vb_grad_k<64, false, 576> : vb_grad_k<64, true, 576>)
+                                : (live_max > 48 ? vb_grad_k<64, false> : vb_grad_k<16, true>);
   hipLaunchKernelGGL(kern, dim3(p.B), dim3(256), lds, st, p);
 }
 

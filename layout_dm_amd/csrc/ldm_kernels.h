@@ -459,9 +459,13 @@ struct VbArgs {
   double* sums;            // [B, 4] kl, nll, aux, hits: sums over the layout's tokens
   float* tok_out;          // (3, B, S) per-token kl, nll, aux, or nullptr
   int32_t* err;            // error word (ldm_vb_core.h kErr*), OR-ed into
+  // vb_grad: sums may be nullptr
+  const double* coef;      // [B, 2] weights of (t == 0 ? nll : kl) and (t == 0 ? nll : aux) in the loss (grad != nullptr)
+  float* grad;             // [B, S, n_class] d loss / d logits, every element written, or nullptr: the sums alone
 };
 void launch_q_sample(const VbArgs& p, hipStream_t st);
 void launch_vb_terms(const VbArgs& p, hipStream_t st);
+void launch_vb_grad(const VbArgs& p, hipStream_t st);
 
 // ---- FID feature extractor (kernels_fid.hip): FIDNetV3.extract_features, trainer/fid/model.py:123-164 -------------
 struct FidLayer {            // nn.TransformerEncoderLayer(256, 4, 128), weights TRANSPOSED to [K][N]

@@ -220,6 +220,93 @@ LDM_PT_HD void token_log_probs(const G& g, const M& m, const TokenArgs& a, const
   token_log_probs(g, m, a, s, q_terms(g, a.tok == a.mask_id, s), l0, lp);
 }
 
+// ---- the posterior WITHOUT cond overrides and its backward, in float64 (the training loss: ldm_vb_core.h token_grad).
+// A float32 evaluation of the backward lands 2 - 4 float32 ulps from the reference's float64 gradient on the classes that carry
+// a gradient near 1, several times the distance the reference's own float32 autograd keeps there; evaluated in float64 from the
+// same float32 inputs (l0 and the schedule entries) and rounded once, an element can be no further from the float64 reference
+// than the nearest float32 is.  exp / log are libm's on the host and on the device.
+LDM_PT_HD double log_add_exp_f64(double a, double b) {
+  const double m = a > b ? a : b;
+  return m + log(exp(a - m) + exp(b - m));
+}
+struct QTermsF64 {
+  double qt_same, qt_other, q1_same, q1_other, q1_mask;
+};
+LDM_PT_HD QTermsF64 q_terms_f64(bool x_is_mask, const StepSchedule& s) {
+  QTermsF64 k;
+  k.q1_same = x_is_mask ? (double)s.lc : log_add_exp_f64(0.0 + (double)s.la, (double)s.lb);
+  k.q1_other = x_is_mask ? (double)s.lc : log_add_exp_f64((double)kLogEps + (double)s.la, (double)s.lb);
+  k.q1_mask = x_is_mask ? 0.0 : (double)kLogEps;
+  k.qt_same = x_is_mask ? (double)s.LC : log_add_exp_f64(0.0 + (double)s.LA, (double)s.LB);
+  k.qt_other = x_is_mask ? (double)s.LC : log_add_exp_f64((double)kLogEps + (double)s.LA, (double)s.LB);
+  return k;
+}
+
+// BACKWARD false: lp[j] = the clamped log-posterior of the lane's live slots (0 elsewhere; up is not read).
+// BACKWARD true:  up[j] = dL/dlp[j] (read on live slots only: the fill value of the others is a constant) -> lp[j] = dL/dl0[j],
+//   0 on [MASK] (its q is the constant log(1e-30)), dead and invalid slots.  With
+//   v_j = clamp(r_j + q1_j + lse, -70, 0),  r_j = log_add_exp(qn_j + LAu, LBu),  qn_j = q_j - lse,
+//   a_j = up[j] where the unclamped v_j lies in [-70, 0] (torch.clamp's backward: both ends pass), else 0,
+//   sigma_j = dr_j / dqn_j = exp(qn_j + LAu - r_j)  ([MASK]: L1Cu, LCu),  p_k = exp(q_k - lse):
+//   dL/dq_k = a_k sigma_k + p_k sum_j a_j (1 - sigma_j)   (log_add_exp's max cancels analytically), and q_k = l0_k - const.
+template <bool BACKWARD, class G, class M>
+LDM_PT_HD void token_log_probs_f64(const G& g, const M& m, const TokenArgs& a, const StepSchedule& s, const QTermsF64& kq,
+                                   const float (&l0)[M::NJ], const double (&up)[M::NJ], double (&lp)[M::NJ]) {
+  constexpr int NJ = M::NJ;
+  const double qt_same = kq.qt_same, qt_other = kq.qt_other, q1_same = kq.q1_same, q1_other = kq.q1_other, q1_mask = kq.q1_mask;
+  double q[NJ];
+  float qmx = -INFINITY;  // (any common shift serves the log-sum-exp: the float32 maximum of the group)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j) {
+    q[j] = 0.0;
+    if (m.live(a, j)) {
+      const int c = m.cls(a, j);
+      q[j] = (c == a.mask_id) ? (double)kLogEps : (double)l0[j] - (c == a.tok ? qt_same : qt_other);
+      qmx = fmaxf(qmx, (float)q[j]);
+    }
+  }
+  qmx = g.gmax(qmx);
+  double qs = 0.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j)
+    if (m.live(a, j)) qs += exp(q[j] - (double)qmx);
+  const double lse = log(g.gsumd(qs)) + (double)qmx;
+  double rest = 0.0;  // sum_j a_j (1 - sigma_j)
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j) {
+    lp[j] = 0.0;
+    if (m.live(a, j)) {
+      const int c = m.cls(a, j);
+      const double arg = (q[j] - lse) + (double)((c == a.mask_id) ? s.L1Cu : s.LAu);
+      const double r = log_add_exp_f64(arg, (double)((c == a.mask_id) ? s.LCu : s.LBu));
+      const double q1 = (c == a.mask_id) ? q1_mask : (c == a.tok ? q1_same : q1_other);
+      const double v = (r + q1) + lse;
+      if (BACKWARD) {
+        const double aj = (v >= -70.0 && v <= 0.0) ? up[j] : 0.0;
+        const double sigma = exp(arg - r);
+        lp[j] = aj * sigma;
+        rest += aj * (1.0 - sigma);
+      } else {
+        lp[j] = v < -70.0 ? -70.0 : (v > 0.0 ? 0.0 : v);
+      }
+    }
+  }
+  if (BACKWARD) {
+    rest = g.gsumd(rest);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < NJ; ++j)
+      lp[j] = (m.live(a, j) && m.cls(a, j) != a.mask_id) ? lp[j] + exp(q[j] - lse) * rest : 0.0;
+  }
+}
+
 // only the [PAD] disabling (the stage between ldm_relation_update and the draw: base.py:272-284)
 template <class M>
 LDM_PT_HD void pad_disable_only(const M& m, const TokenArgs& a, float (&lp)[M::NJ]) {

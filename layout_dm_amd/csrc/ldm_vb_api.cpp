@@ -1,7 +1,8 @@
 // Host side of scoring GIVEN layouts (include/ldm_hip.h: ldm_q_sample, ldm_vb_terms, ldm_vb_step): the forward noising draw,
 // the variational bound's terms of one timestep, and the two around one denoiser pass of the handle's own numerics mode — at ONE
 // timestep for the call, or (ldm_q_sample_t, ldm_vb_terms_t, ldm_vb_step_t) at a timestep per layout, one body for both.
-// Evaluation of a trained model only: no gradients, nothing of the handle's weights or schedule is written.
+// Evaluation of a trained model, and (ldm_vb_grad) the training loss's gradient with respect to GIVEN logits: nothing of the handle's
+// weights or schedule is written.
 // Tokens are checked by the kernels (ldm_vb_core.h token_error) into an error word the call reads back before it returns:
 // a refused call has synchronised the stream, like a successful one.
 #include "ldm_handle.h"
@@ -160,7 +161,46 @@ int vb_step(ldm_handle* h, const int32_t* d_x0, const int32_t* d_xt, int t, cons
   return err_end(h, st);
 }
 
+// ldm_vb_grad runs no denoiser, so it takes per-layout timesteps on every handle: stage_timesteps without its engine check
+int stage_grad_timesteps(ldm_handle* h, const int32_t* h_t, int B, hipStream_t st, const int32_t** d_t) {
+  for (int b = 0; b < B; ++b)
+    if (h_t[b] < 0 || h_t[b] >= h->T) return h->fail(-1, "timestep %d of layout %d out of range [0,%d)", h_t[b], b, h->T);  // constrained.py:139
+  if (!h->st_t) {
+    int rc = h->dalloc(&h->st_t, (size_t)h->cfg.max_batch);
+    if (rc) return rc;
+    h->st_t_host.resize((size_t)h->cfg.max_batch);
+  }
+  std::copy(h_t, h_t + B, h->st_t_host.begin());
+  HIP_OK(h, hipMemcpyAsync(h->st_t, h->st_t_host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  *d_t = h->st_t;
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int ldm_vb_grad(ldm_handle* h, const float* d_logits, const int32_t* d_x0, const int32_t* d_xt, const int32_t* h_t, int B,
+                           const double* d_coef, float* d_grad, double* d_sums, void* stream) {
+  int rc = check_ready(h, B);
+  if (rc) return rc;
+  if (!d_logits || !d_x0 || !d_xt || !h_t || (!d_grad && !d_sums) || (d_grad && !d_coef)) return h->fail(-1, "null argument");
+  ON_DEVICE(h);
+  hipStream_t st = (hipStream_t)stream;
+  CallT c;
+  if ((rc = stage_grad_timesteps(h, h_t, B, st, &c.d_t))) return rc;
+  if ((rc = err_begin(h, st))) return rc;
+  VbArgs p{};
+  fill_vb(h, p, c, 0, B);
+  p.f32_lse = 0;   // the logits are the caller's: the reference's float64 log-softmax whatever the handle's numerics mode
+  p.logits = d_logits;
+  p.ldl = h->plan.C;
+  p.x0 = d_x0;
+  p.xt = d_xt;
+  p.sums = d_sums;
+  p.coef = d_coef;
+  p.grad = d_grad;
+  launch_vb_grad(p, st);
+  return err_end(h, st);
+}
 
 extern "C" int ldm_q_sample(ldm_handle* h, const int32_t* d_x0, int t, uint64_t seed, uint64_t first_layout, int B,
                             int32_t* d_xt, void* stream) {

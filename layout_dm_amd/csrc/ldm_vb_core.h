@@ -8,6 +8,8 @@
 //                    nll = -sum_c exp(log_onehot(x_0)) model                                    util.py:30-31
 //                    aux = KL(log_onehot(x_0)[:-1] || log_x0_recon[:-1])                        constrained.py:317-319
 //                    hit = argmax log_x0_recon == x_0                                           constrained.py:269-277
+//   token_grad       d / d logits of  c_kl (t == 0 ? nll : kl) + c_aux (t == 0 ? nll : aux)  for the token: the training loss's
+//                    backward behind the logits (constrained.py:292-330 under autograd), closed form, float64
 //
 // The lane groups, the slot maps, the schedule rows, QTerms and the posterior itself are those of ldm_post_token.h.  A token's
 // sub-vocabulary (body + [PAD] + [MASK]; vanilla: every class) carries the posterior; every other class sits at log(1e-30) in
@@ -114,8 +116,13 @@ struct Terms {
 // F64_LSE: the reference's float64 log-softmax; otherwise fp32 (the fast numerics mode).  Every lane of the group returns the
 // token's terms.  Float32 sums: a lane's slots / classes in increasing order, then the group's tree.
 // RECON (host check only): a.logits IS log_x0_recon — the reference's own, so that the check isolates what follows it.
+// rs (token_grad): receives the row's maximum and float64 log-sum-exp.
+struct RowStats {
+  float mx;
+  double lse;
+};
 template <bool F64_LSE, class G, class M, bool RECON = false>
-LDM_PT_HD Terms token_terms(const G& g, const M& m, const TokenArgs& a_in, int x0, const StepSchedule& s) {
+LDM_PT_HD Terms token_terms(const G& g, const M& m, const TokenArgs& a_in, int x0, const StepSchedule& s, RowStats* rs = nullptr) {
   constexpr int NJ = M::NJ;
   TokenArgs a = a_in;
   a.cond_tok = -1;
@@ -139,6 +146,10 @@ LDM_PT_HD Terms token_terms(const G& g, const M& m, const TokenArgs& a_in, int x
     float se = 0.f;
     for (int c = g.lane(); c < C1; c += G::NL) se += g.exp(a.logits[c] - mx);
     lse0f = g.log(g.gsum(se));
+  }
+  if (rs) {
+    rs->mx = mx;
+    rs->lse = lse0d;
   }
   auto recon = [&](int c) {  // log_x0_recon of a non-MASK class
     return RECON ? a.logits[c] : F64_LSE ? ldm_post::l0_f64(a.logits[c], mx, lse0d) : ldm_post::l0_f32(a.logits[c], mx, lse0f);
@@ -185,6 +196,91 @@ LDM_PT_HD Terms token_terms(const G& g, const M& m, const TokenArgs& a_in, int x
   out.nll = -g.gsum(nll);
   out.aux = aux;
   out.hit = bi == x0 ? 1 : 0;
+  return out;
+}
+
+// The gradient of one token's share of the training loss with respect to its row of logits (constrained.py:292-330):
+//   L = c_kl (t == 0 ? nll : kl) + c_aux (t == 0 ? nll : aux)
+// with the token's terms as token_terms<true> computes them — the forward is that very call (float64 log-sum-exp, the
+// reference's precision), so the returned terms carry its bits.  grad_row[c], c = 0 .. C - 1, receives dL/dlogit[c]; the [MASK]
+// column is 0.  Every element of the row is written exactly once: a lane writes the classes of its own slots, and — LIVE maps —
+// the classes outside the token's sub-vocabulary lane-strided, consecutive lanes consecutive classes.
+//   upstream of the posterior   kl: dL/dlpm[j] = -c_kl exp(lpt[j]) (base.py:117-119; the true posterior is a constant);
+//                               nll: -(c_kl + c_aux)(cls(j) == x0 ? 1 : e30); the log(1e-30) fill of dead classes carries nothing
+//   through the posterior       ldm_post_token.h token_log_probs_f64 -> dL/dl0 on the live non-[MASK] slots
+//   aux                         -c_aux (c == x0 ? 1 : e30) on every one of the C - 1 classes
+//   through l0 = clamp(log_softmax, -70, 0)   gate by the clamp (both ends pass), then as the reference's
+//                               log_softmax(out.double()) runs its backward: dlogit_c = gl0_c - softmax_c sum_k gl0_k
+template <class G, class M>
+LDM_PT_HD Terms token_grad(const G& g, const M& m, const TokenArgs& a_in, int x0, const StepSchedule& s, double c_kl, double c_aux,
+                           bool t_is_zero, float* grad_row) {
+  constexpr int NJ = M::NJ;
+  TokenArgs a = a_in;
+  a.cond_tok = -1;
+  a.strong = false;
+  a.weak = nullptr;
+  a.pad_disable = false;
+  RowStats rs;
+  const Terms out = token_terms<true>(g, m, a, x0, s, &rs);
+  const int C1 = a.n_class - 1;
+  const float e30 = g.exp(kLogEps);
+  const double w_post = t_is_zero ? c_kl + c_aux : c_kl;  // on nll (t == 0) or kl
+  const double w_aux = t_is_zero ? 0.0 : c_aux;
+  auto lsm = [&](int c) { return ((double)a.logits[c] - (double)rs.mx) - rs.lse; };  // log-softmax of a non-MASK class, float64
+  auto passes = [&](double u) { return (float)u >= -70.0f && (float)u <= 0.0f; };
+  auto aux_grad = [&](int c) { return w_aux == 0.0 ? 0.0 : -(w_aux * (double)(c == x0 ? 1.0f : e30)); };
+  // ---- the posterior path on the token's slots, in float64 from the float32 l0 (ldm_post_token.h token_log_probs_f64)
+  float l0m[NJ], l0t[NJ];
+  double up[NJ], gs[NJ];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j) {
+    const int c = m.cls(a, j);
+    l0m[j] = (m.valid(a, j) && c < C1) ? ldm_post::l0_f64(a.logits[c], rs.mx, rs.lse) : -70.0f;
+    l0t[j] = c == x0 ? 0.0f : kLogEps;
+    up[j] = -(w_post * (double)(c == x0 ? 1.0f : e30));
+  }
+  const ldm_post::QTermsF64 kq = ldm_post::q_terms_f64(a.tok == a.mask_id, s);
+  if (!t_is_zero) {
+    double lpt[NJ];
+    ldm_post::token_log_probs_f64<false>(g, m, a, s, kq, l0t, up, lpt);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int j = 0; j < NJ; ++j) up[j] = m.live(a, j) ? -(w_post * exp(lpt[j])) : 0.0;
+  }
+  ldm_post::token_log_probs_f64<true>(g, m, a, s, kq, l0m, up, gs);
+  // ---- gl0 per class: both paths added, rounded to float32 (the type of the reference's log-softmax output, and so of its
+  // gradient, whatever the module's), gated by the clamp; and its sum over the row
+  double tot = 0.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j) {
+    const int c = m.cls(a, j);
+    gs[j] = (m.valid(a, j) && c < C1 && passes(lsm(c))) ? (double)(float)(gs[j] + aux_grad(c)) : 0.0;
+    tot += gs[j];
+  }
+  if (M::LIVE && w_aux != 0.0)
+    for (int c = g.lane(); c < C1; c += G::NL)
+      if (!ldm_post::is_live(a, c) && passes(lsm(c))) tot += (double)(float)aux_grad(c);
+  tot = g.gsumd(tot);
+  // ---- through the log-softmax, and out
+  if (M::LIVE)
+    for (int c = g.lane(); c < a.n_class; c += G::NL)
+      if (!ldm_post::is_live(a, c)) {  // (below C - 1: [MASK] is live)
+        const double u = lsm(c);
+        grad_row[c] = (float)((passes(u) ? (double)(float)aux_grad(c) : 0.0) - exp(u) * tot);
+      }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+  for (int j = 0; j < NJ; ++j)
+    if (m.valid(a, j)) {
+      const int c = m.cls(a, j);
+      grad_row[c] = c < C1 ? (float)(gs[j] - exp(lsm(c)) * tot) : 0.0f;
+    }
   return out;
 }
 
