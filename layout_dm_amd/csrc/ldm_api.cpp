@@ -374,8 +374,8 @@ extern "C" int ldm_describe(const ldm_handle* h, char* buf, int cap) {
   // the denoiser variant, named only where it is not the default (elem_attr positions, adalayernorm): ldm_create_variant's norm1 kind and what
   // ldm_finalize_weights read from the checkpoint's key set
   if (h->plan.instance_norm) s += ";norm1=instance";
-  if (h->pos_default) s += ";pos_emb=default";
-  if (h->timestep_kind != ldm_handle::kTimestepLearned) s += std::string(";timestep_emb=") + (h->timestep_kind == ldm_handle::kTimestepAbs ? "abs" : "none");
+  if (h->wplan.pos_default) s += ";pos_emb=default";
+  if (h->wplan.timestep_kind != kTimestepLearned) s += std::string(";timestep_emb=") + (h->wplan.timestep_kind == kTimestepAbs ? "abs" : "none");
   s += ";knobs=" + knobs_honoured();
   if (buf && cap > 0) {
     const size_t n = std::min((size_t)cap - 1, s.size());

@@ -22,6 +22,10 @@ constexpr int kStackStep0Floats = 5 * 16 * 256;   // step-0 logits of one layout
 constexpr int kStackPostMaxLive = 48;             // largest sub-vocabulary (body + [PAD] + [MASK]) the fused tail takes: 3 class slots on each of a group's 16 lanes
 constexpr int kStep0Slots = 4;                    // (first timestep, S) keys of the step-0 logits cache
 constexpr int kSchedRows = 8;                     // schedule buffers per attribute (ldm_kernels.h ScheduleRow)
+// parameter tables of the loop kernel as LDS images, in floats (kernels_stack.hip HEAD == 2)
+constexpr int kStackTblAttStatic = 1536;  // in_proj bias [3 * 8 heads * 64]
+constexpr int kStackTblAttDyn = 1536;     // 1 + AdaLN scale [512] | shift [512] | b_out + W_out b_v + shift [512]
+constexpr int kStackTblFfn = 3584;        // linear1 bias [2048] | norm2 gamma [512] | beta [512] | linear2 bias [512]
 
 // ---- geometry rules shared with the launchers (which add their pointer, stride and alignment checks)
 // fused attention + out_proj (kernels_attnout.hip): one 128-row tile per layout, the reference's 8 heads of 58

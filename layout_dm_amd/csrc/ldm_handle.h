@@ -2,6 +2,8 @@
 // buffers, hipGraph cache, profiling) and the helpers the translation units of the C-ABI share.
 //   ldm_engine_plan.h  which engine a configuration runs, its geometry and buffer sizes — or why it is refused (host-pure; ldm_handle::plan)
 //   ldm_api.cpp      lifecycle, parity hooks, result packaging, near-tie report, introspection
+//   ldm_weight_plan.h  what a checkpoint is to the handle: variant, keys read, the size of every derived buffer — or why it is refused; the
+//                      split mode's weight cast (host-pure; ldm_handle::wplan)
 //   ldm_weights.cpp  checkpoint upload, fp16 / LDS weight images, parameter tables (ldm_load_weight / ldm_finalize_weights)
 //   ldm_denoise.cpp  the launch sequence of one denoiser pass over a chunk, per numerics mode
 //   ldm_vb_api.cpp   scoring given layouts: forward noising draw, variational-bound terms (ldm_q_sample / ldm_vb_terms / ldm_vb_step)
@@ -24,6 +26,7 @@
 #include "ldm_kernels.h"
 #include "ldm_loop_plan.h"
 #include "ldm_pack.h"
+#include "ldm_weight_plan.h"
 
 using namespace ldm;
 
@@ -58,8 +61,13 @@ struct DeviceGuard {
   if (_dev_guard.err != hipSuccess) return (h)->fail(-2, "hipSetDevice(%d) failed: %s", (h)->device,    \
                                                      hipGetErrorString(_dev_guard.err))
 
-struct Raw {  // a checkpoint tensor as uploaded (fp32, device)
+struct Raw {  // a checkpoint tensor as loaded, fp32: the device copy the exact engine and the table kernels read, and the host copy the
+              // images, padded copies and tables are built from (one pass, one upload per buffer) — kept where this handle's engine builds
+              // from it: every vector (biases, norms, schedules), and the matrices of a handle that packs fp16 images from them (fast,
+              // hybrid's fused FFN); a split-type handle needs of a matrix only its scale
   float* d = nullptr;
+  std::vector<float> host;
+  float split_scale = 1.f;   // split-type handles, matrices: ldm_weight_plan.h split_scale of the tensor
   std::vector<int64_t> shape;
   int64_t numel() const {
     int64_t n = 1;
@@ -164,10 +172,8 @@ struct ldm_handle {
   // weights
   std::map<std::string, Raw> raw;
   bool finalized = false;
-  // the denoiser variant ldm_finalize_weights read from the key set (ldm_describe names it where it is not the default)
-  enum { kTimestepLearned = 0, kTimestepAbs = 1, kTimestepNone = 2 };   // norm1.emb.weight | the sinusoid | nn.LayerNorm, constant in t
-  bool pos_default = false;   // transformer.pos_emb.pos_emb instead of the elem_emb / attr_emb pair
-  int timestep_kind = kTimestepLearned;
+  WeightPlan wplan;    // what the last ldm_finalize_weights read from the key set: the denoiser variant (ldm_describe names it where it is not
+                       // the default), the keys, the derived buffers' sizes (ldm_weight_plan.h)
   std::vector<LayerW> layers;
   float *pos = nullptr, *adaln = nullptr, *sched = nullptr;
   const float *emb = nullptr, *head_g = nullptr, *head_b = nullptr, *head_w = nullptr;
@@ -177,7 +183,6 @@ struct ldm_handle {
   std::vector<void*> owned;    // everything hipMalloc'ed by the handle for its lifetime
   std::vector<void*> derived;  // what ldm_finalize_weights derives from the checkpoint (fp16 / split copies, LDS images, parameter
                                // tables): freed and rebuilt when the weights are finalized again (a reload used to leak them)
-  bool to_derived = false;     // dalloc's destination while ldm_finalize_weights runs
   int n_cu = 256;              // compute units of the device: the batch quantum of the one-launch loop (one workgroup per layout)
   // Lanes (plan.n_lanes, plan.lane_offset_us): chunks c, c + n_lanes, ... form lane (c % n_lanes); every lane has its own workspace (ws[lane]: what its launches
   // and its captured graph are given), stream and captured graph, and the lanes run CONCURRENTLY, lane l starting
@@ -257,8 +262,9 @@ struct ldm_handle {
     return code;
   }
 
+  // `into`: the list that owns the allocation — `owned`, or `derived` (ldm_weights.cpp)
   template <typename Tp>
-  int dalloc(Tp** out, size_t count, bool zero = true) {
+  int dalloc(Tp** out, size_t count, bool zero = true, std::vector<void*>* into = nullptr) {
     void* p = nullptr;
     const size_t bytes = std::max<size_t>(count * sizeof(Tp), 16);
     hipError_t e = hipMalloc(&p, bytes);
@@ -267,7 +273,7 @@ struct ldm_handle {
       e = hipMemset(p, 0, bytes);
       if (e != hipSuccess) return fail(-3, "hipMemset failed: %s", hipGetErrorString(e));
     }
-    (to_derived ? derived : owned).push_back(p);
+    (into ? *into : owned).push_back(p);
     *out = reinterpret_cast<Tp*>(p);
     return 0;
   }
