@@ -633,7 +633,11 @@ class Engine:
         assert logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous()
         lr, keep = rel
         cond_seq = self._tok(cond_seq)
-        assert layout_offset == 0, "relation graphs are indexed from the first layout of the call"
+        if layout_offset:   # a window of the plan: `logp` / `cond_seq` hold layouts layout_offset .. of it (the step stays the plan's)
+            from .relation import _relation_window
+
+            assert 0 < layout_offset and layout_offset + logp.shape[0] <= lr.n_graph_total, "window outside the relation plan"
+            lr, keep = _relation_window(rel, int(layout_offset))
         self._check(self.lib.ldm_relation_update(self._h, logp.data_ptr(), cond_seq.data_ptr(), C.byref(lr), int(t),
                                                  logp.shape[0], _stream_ptr(self.device)), "ldm_relation_update")
         torch.cuda.current_stream(self.device).synchronize()  # cond_seq copy / keep-alives may be temporaries

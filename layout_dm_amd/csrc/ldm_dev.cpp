@@ -3,7 +3,8 @@
 // synthetic operands (tests/test_attnout_gpu.py), and one row-resident LayerNorm + GEMM launch of a live handle on the caller's rows
 // (ldm_dev_lngemm_run, tests/test_lngemm_gpu.py), and one fused attention + out_proj (+ FFN) launch of a live handle on the caller's panels
 // (ldm_dev_attnout_run, tests/test_attnout_kernel_gpu.py), and one launch of a LayerNorm / GEMM / attention kernel of the tiled engines on the caller's
-// buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py), and the counters of the
+// buffers (ldm_dev_layernorm_run, ldm_dev_gemm_run, ldm_dev_attention_run, tests/test_tiled_kernels_gpu.py), and one launch of the relation logit-adjustment kernel on the caller's buffers (ldm_dev_relation_run,
+// tests/test_relation_kernel_gpu.py), and the counters of the
 // handle's cache of captured loops (ldm_dev_graph_cache, tests/test_loop_graph_cache_gpu.py).  Nothing in the product path calls into this file.
 #include <hip/hip_runtime.h>
 
@@ -437,5 +438,64 @@ extern "C" int ldm_dev_attention_run(const ldm_dev_attention_io* io) {
   a.B = B; a.S = S; a.H = H; a.dh = dh; a.D = io->D; a.ld = io->ld; a.ldo32 = io->ldo32; a.ldo16 = io->ldo16;
   (void)hipGetLastError();
   launch_attention(a, 0);
+  return dev_launched();
+}
+
+// ONE relation_update_k launch (kernels_relation.hip: the SGD of ldm_relation_core.h on a (B,C,S) or (B,S,C) tensor) on the caller's device
+// buffers, without a handle (tests/test_relation_kernel_gpu.py).  The io struct mirrors RelArgs and carries the capacity of every buffer; no
+// reference arithmetic here (tests/_relation_cases.py holds the float64 side).  -1, before any launch, for whatever the kernel's stated
+// preconditions forbid — the kernel itself checks nothing, so the small integer arrays (offsets, node ids, the conditioned categories that
+// decide which elements are nodes) are copied to the host and checked here; the launch runs on the current device's null stream; -2 on a
+// HIP error.  num_update <= 0 and B == 0 go through launch_relation_update like any call: it launches nothing.
+#include "ldm_relation_core.h"   // (REL_MAX_ELEM)
+struct ldm_dev_relation_io {    // RelArgs
+  float* logp;
+  const int32_t *cond_seq, *edge_off, *edge_src, *edge_dst, *edge_attr;
+  const float* centres;
+  int32_t canvas_bins[4];
+  float step;
+  int32_t num_update, B, C, S, A, n_category, n_bin, pad_id, logp_tm;
+  int64_t logp_floats, n_cond, n_edge_off, n_edge, n_centres;   // capacities in elements (n_edge: of each of the three edge arrays)
+};
+extern "C" int ldm_dev_relation_run(const ldm_dev_relation_io* io) {
+  if (!io) return -1;
+  const int64_t B = io->B, C = io->C, S = io->S, A = io->A, NB = io->n_bin;
+  if (B < 0 || io->num_update < 0 || (io->logp_tm != 0 && io->logp_tm != 1)) return -1;
+  // a token's four coordinates sit behind its category (position e A + 1 + x); one workgroup holds E x 4 x 32 logits and 33 boxes in LDS
+  if (A != 5 || S < A || S % A || S / A > REL_MAX_ELEM || NB < 1 || NB > 32) return -1;
+  if (io->n_category < 0 || C < io->n_category + 4 * NB) return -1;
+  if (!io->logp || !io->cond_seq || !io->edge_off || !io->centres || !aligned(io->logp, 4) || !aligned(io->centres, 4)) return -1;
+  if (io->n_edge < 0 || (io->n_edge > 0 && (!io->edge_src || !io->edge_dst || !io->edge_attr))) return -1;
+  if (io->logp_floats < B * C * S || io->n_cond < B * S || io->n_edge_off < B + 1 || io->n_centres < 4 * NB) return -1;
+  for (int x = 0; x < 4; ++x)
+    if (io->canvas_bins[x] < 0 || io->canvas_bins[x] >= NB) return -1;
+  if (B > 0) {   // (the bounds that need the operands' values)
+    std::vector<int32_t> off((size_t)B + 1), seq((size_t)(B * S));
+    if (hipMemcpy(off.data(), io->edge_off, off.size() * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(seq.data(), io->cond_seq, seq.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return -2;
+    if (off[0] < 0 || off[B] > io->n_edge) return -1;
+    for (int64_t b = 0; b < B; ++b)
+      if (off[b + 1] < off[b]) return -1;
+    const size_t n = (size_t)(off[B] - off[0]);
+    std::vector<int32_t> src(n), dst(n);
+    if (n && (hipMemcpy(src.data(), io->edge_src + off[0], n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+              hipMemcpy(dst.data(), io->edge_dst + off[0], n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+      return -2;
+    for (int64_t b = 0; b < B; ++b) {
+      int nodes = 0;   // node 0 is the canvas; elements with a category are nodes 1 .. nodes, in element order
+      for (int64_t e = 0; e < S / A; ++e) nodes += seq[(size_t)(b * S + e * A)] != io->pad_id;
+      for (int32_t k = off[b] - off[0]; k < off[b + 1] - off[0]; ++k)
+        if (src[k] < 0 || src[k] > nodes || dst[k] < 0 || dst[k] > nodes) return -1;
+    }
+  }
+  RelArgs a{};
+  a.logp = io->logp; a.cond_seq = io->cond_seq; a.edge_off = io->edge_off; a.edge_src = io->edge_src; a.edge_dst = io->edge_dst;
+  a.edge_attr = io->edge_attr; a.centres = io->centres;
+  for (int x = 0; x < 4; ++x) a.canvas_bins[x] = io->canvas_bins[x];
+  a.step = io->step; a.num_update = io->num_update; a.B = (int)B; a.C = (int)C; a.S = (int)S; a.A = (int)A;
+  a.n_category = io->n_category; a.n_bin = (int)NB; a.pad_id = io->pad_id; a.logp_tm = io->logp_tm;
+  (void)hipGetLastError();
+  launch_relation_update(a, 0);
   return dev_launched();
 }
