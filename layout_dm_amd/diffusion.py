@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from .binding import Engine
+from .selection import FP16_MAX_CLASSES, RUNGS, THROUGHPUT_CLASS  # noqa: F401  (theirs, under the names they had here)
+from .selection import Selector, selection_message, selection_report
 
 _seed_counter = itertools.count()
 # the reference's entry point logs at INFO (trainer/test.py:38); `precision="auto"` says here which engine a checkpoint got and why
@@ -45,26 +47,24 @@ def variant_name(pos_emb: str, timestep_type) -> Optional[str]:
     return ", ".join(parts) or None
 
 
-FP16_MAX_CLASSES = 192   # ldm_create: fast / mixed / hybrid refuse wider vocabularies; exact / split take up to 576 classes, 128 bins
-# what each engine delivers on one MI355X (Rico25-shaped sequences, T = 100, batch 512; bench.py measures it on the box at hand)
-THROUGHPUT_CLASS = {
-    "fast": "~3 900 layouts/s (fp16 operands, one launch per sampling call)",
-    "fast_verified": "~3 400 - 3 900 layouts/s (fp16 engine; greedy decoding re-checked by the reference-precision engine)",
-    "hybrid": "~2 200 layouts/s (attention path: hi + lo fp16 activations x fp16 weights; FFN and head in plain fp16; per-step launches)",
-    "hybrid_verified": "~2 200 layouts/s (attention path hi + lo x fp16, FFN / head plain fp16; greedy decoding re-checked by the reference-precision engine)",
-    "mixed": "~1 500 layouts/s (hi + lo fp16 activations x fp16 weights: two matrix passes per weight product, per-step launches)",
-    "mixed_verified": "~1 500 layouts/s (hi + lo fp16 activations x fp16 weights; greedy decoding re-checked by the reference-precision engine)",
-    "split": "~1 150 - 1 200 layouts/s (reference precision on the fp16 matrix pipe, per-step launches)",
-    "exact": "~420 layouts/s (fp32 MFMA)",
-}
-
-
 def _cfg_get(cfg, key, default=None):
     if cfg is None:
         return default
     if hasattr(cfg, "get"):
         return cfg.get(key, default)
     return getattr(cfg, key, default)
+
+
+def schedule_and_seed(num_timesteps: int, sampling_cfg, seed: Optional[int]):
+    """(t_model, t_post, seed) of one sampling call: the schedule sampling_cfg asks for, and the Philox key — `seed`, or one drawn
+    from torch's global CPU generator.  Deterministic decoding draws nothing — and must not advance that generator either: the
+    reference's argmax path consumes no random numbers (helpers/sampling.py:110-111), and test.py's get_cond of the NEXT batch
+    reads that stream."""
+    t_model, t_post = timestep_schedule(num_timesteps, int(_cfg_get(sampling_cfg, "num_timesteps", num_timesteps)),
+                                        float(_cfg_get(sampling_cfg, "time_difference", 0.0) or 0.0))
+    if seed is None:
+        seed = 0 if str(_cfg_get(sampling_cfg, "name")) == "deterministic" else int(torch.randint(0, 2 ** 62, (1,)).item())
+    return t_model, t_post, seed
 
 
 def batch_cuts(B: int, max_batch: int, round_: int) -> List[int]:
@@ -134,21 +134,8 @@ class HipMaskAndReplaceDiffusion:
                  verifier: str = "split", auxiliary_loss_weight: float = 1e-1, pos_emb: str = "elem_attr",
                  timestep_type: Optional[str] = "adalayernorm"):
         # q_type: Q_TYPES of models/layoutdm.py:20-23 — "constrained" (constrained.py) or "vanilla" (vanilla.py)
-        # precision "fast_verified": the fp16 engine for every sampler, plus an exact (fp32) engine of the same weights
-        # that re-decides the near-tie layouts of DETERMINISTIC decoding (layout_dm_amd/verified.py): greedy tokens are
-        # then the exact mode's, i.e. the reference's, bit for bit
-        # precision "auto" (r04): both engines are built; load_state_dict measures the fp16 engine's logits error against the
-        # fp32 engine ON THE CHECKPOINT (verified.measure_fast_error: probe states over the whole timestep range) and keeps
-        # the fast engine only if it is inside the north star's 1e-3 relative tolerance — otherwise every call runs exact.
-        # (The fp16 mode's error is a property of the weights: 3e-4 on the reference's init, ~1e-3 at sigma = 0.06,
-        # percents once attention rows saturate: DESIGN.md section 3.5.)
-        # r06: a rung between the two — "mixed" (LDM_PREC_MIXED_F16: the split mode with fp16-only WEIGHTS, two matrix passes per weight
-        # product instead of three, +19 % over split; its logits error is 2e-4 on a fitted checkpoint whose fp16 error is 1.2e-3).  When the
-        # fp16 engine is outside the tolerance, auto builds a mixed engine, measures IT the same way, and keeps it — again with verified
-        # greedy decoding — if it is inside; only then the reference-precision engine runs every call.  "mixed" / "mixed_verified" select it
-        # unconditionally.  In front of it sits "hybrid" (LDM_PREC_HYBRID_F16: mixed with the FFN and the head in plain fp16 — the fp16 error
-        # lives on the attention-score path; 2.8e-4 on the fitted checkpoint), so auto's ladder is fast -> hybrid -> mixed -> reference precision,
-        # each rung built on first need and held to the same measurement.
+        # precision / verifier: selection.py — an engine's name, "<name>_verified", or "auto": load_state_dict measures the fp16
+        # engine on the checkpoint and selects
         # pos_emb / timestep_type: the denoiser variants of the reference's constructor (nn_lib.py:73-127, transformer_utils.py:124-156).
         # The library reads pos_emb, the *_abs sinusoid and timestep_type None from the checkpoint's key set and serves them on every
         # engine; the two adainnorm kinds (instance norm over a layout's rows: the state dict does not tell them from adalayernorm)
@@ -158,60 +145,30 @@ class HipMaskAndReplaceDiffusion:
         check_timestep_type(timestep_type)
         self.pos_emb, self.timestep_type = pos_emb, timestep_type
         self.instance_norm = timestep_type in INSTANCE_NORM_TYPES
-        self.verified = None
-        self._v_fast = None                      # VerifiedGreedy(fp16 engine, verifier)
-        self._v_rung: Dict[str, object] = {}     # rung -> VerifiedGreedy(its engine, verifier), built on first need
-        self._rung_error: Dict[str, Dict[str, float]] = {}   # rung -> what auto measured on the checkpoint loaded last
-        self.verifier = verifier
+        self.wide_vocab = n_category + 4 * n_bin + 2 > FP16_MAX_CLASSES
+        self.precision = precision
         self.auto = precision == "auto"
         self.auto_tolerance = 1e-3
         self.verifier_tolerance = 5e-4     # split vs a small fp32-MFMA probe engine: half the north star's tolerance (two valid fp32-level
                                            # engines differ by 4.2e-4 on the "wide" point, where the reference's own f32 noise floor is 1.2e-4)
-        self.verifier_check: Dict[str, float] = {}
-        self.selection_report: Dict[str, object] = {}
-        self.selected_precision = None if self.auto else precision
-        self._mk = mk = lambda prec, mb=max_batch: Engine(n_category=n_category, n_bin=n_bin, max_elem=max_elem, n_attr=n_attr,
-                                 d_model=d_model, n_head=n_head, d_ff=d_ff, n_layer=n_layer, n_step=num_timesteps,
-                                 precision=prec, max_batch=mb, chunk=chunk, device=device, q_type=q_type,
-                                 lanes=lanes, timestep_type=timestep_type)
-        # wide vocabularies (64 / 128 bins per coordinate): the fp16 engines stop at FP16_MAX_CLASSES classes (ldm_create), the
-        # reference-precision engines at 576.  auto then IS its reference-precision engine — no fp16 engine is built or measured —
-        # and every name that needs an fp16 engine is refused with the library's own message
-        n_class = n_category + 4 * n_bin + 2
-        self.wide_vocab = n_class > FP16_MAX_CLASSES
-        if self.wide_vocab and precision != "auto" and precision not in ("exact", "split"):
-            try:
-                mk(precision[:-len("_verified")] if precision.endswith("_verified") else precision)
-            except RuntimeError as e:
-                if "192 classes" not in str(e):
-                    raise
-                raise NotImplementedError(str(e)) from e
-        if self.instance_norm and precision != "auto" and precision not in ("exact", "split"):
-            try:
-                mk(precision[:-len("_verified")] if precision.endswith("_verified") else precision)
-            except RuntimeError as e:
-                if "adainnorm" not in str(e):
-                    raise
-                raise NotImplementedError(str(e)) from e
-        if (self.wide_vocab or self.instance_norm) and self.auto:
-            assert verifier in ("split", "exact")
-            self.engine = mk(verifier)
-            self.selected_precision = verifier
-        elif precision in ("fast_verified", "mixed_verified", "hybrid_verified", "auto"):
-            from .verified import VerifiedGreedy
 
-            # the reference-precision engine behind fast_verified / mixed_verified / auto: "split" (fp16 x 3 on the fp16 matrix
-            # pipe: the exact mode's logits error at 1.7 x its speed, r04) or "exact" (fp32 MFMA)
-            assert verifier in ("split", "exact")
-            self.engine = mk(precision[:-len("_verified")] if precision in ("mixed_verified", "hybrid_verified") else "fast")
-            self.verified = self._v_fast = VerifiedGreedy(self.engine, mk(verifier))
-        else:
-            self.engine = mk(precision)
+        def mk(prec, mb=max_batch):
+            return Engine(n_category=n_category, n_bin=n_bin, max_elem=max_elem, n_attr=n_attr, d_model=d_model, n_head=n_head,
+                          d_ff=d_ff, n_layer=n_layer, n_step=num_timesteps, precision=prec, max_batch=mb, chunk=chunk,
+                          device=device, q_type=q_type, lanes=lanes, timestep_type=timestep_type)
+
+        self._selector = sel = Selector(mk, precision, verifier, self.auto_tolerance, self.verifier_tolerance, self.wide_vocab,
+                                        timestep_type if self.instance_norm else None)
+        # which engine runs: load_state_dict alone changes these, from what the selector returns
+        self.engine, self.verified = sel.primary, sel.v_fast
+        self.selected_precision, self.verifier = sel.selected, verifier
+        self._v_fast, self._v_rung = sel.v_fast, sel.v_rung    # the fp16 pair (or None) and the pairs of the rungs auto has built so far
+        self.verifier_check: Dict[str, object] = {}
+        self.selection_report: Dict[str, object] = {}
         self.q_type = q_type
         self.num_timesteps = num_timesteps
         self.num_classes = self.engine.C
         self.max_token_length = self.engine.S
-        self.precision = precision
         self.use_graph = use_graph
         self.mask_id = self.engine.mask_id
         self.pad_id = self.engine.pad_id
@@ -221,6 +178,8 @@ class HipMaskAndReplaceDiffusion:
         self.adaptive_auxiliary_loss = True
         self.Lt_history: Optional[torch.Tensor] = None
         self.Lt_count: Optional[torch.Tensor] = None
+
+    RUNGS = RUNGS
 
     # -- nn.Module-ish surface used by the reference's callers --------------------------------
     @property
@@ -233,186 +192,23 @@ class HipMaskAndReplaceDiffusion:
     def eval(self):
         return self
 
-    def _check_verifier(self, state_dict) -> None:
-        """auto / fast_verified treat the verifier engine as ground truth: check THAT once per checkpoint.  The
-        split engine rounds every operand to an fp16 hi part (overflow above 65 504) and an unscaled fp16 lo part, so it is
-        compared with a small fp32-MFMA engine of the same weights on two probe states; if its logits are non-finite or
-        differ by more than `verifier_tolerance` the fp32-MFMA engine becomes the verifier, and if that one is non-finite
-        too the checkpoint is refused here, at load time — not at the first sampling call."""
-        from .verified import measure_fast_error, probe_states
-
-        v = self.verified
-        n = max(1, min(4, int(v.exact.max_batch)))   # (ADVICE r5: the probe batch must fit an engine built with max_batch < 4)
-        if self.verifier != "split":
-            states = probe_states(v.exact, n_layouts=n, ts=[v.exact.T // 2])
-            lg = v.exact.denoise_logits(*states[0])
-            if not bool(torch.isfinite(lg).all()):
-                raise FloatingPointError("reference-precision engine: non-finite logits on this checkpoint")
-            self.verifier_check = {"verifier": self.verifier, "finite": True}
-            return
-        small = self._mk("exact", n)
-        try:
-            small.load_state_dict(state_dict)
-            states = probe_states(small, n_layouts=n, ts=[small.T - 1, small.T // 2, 1])
-            c = measure_fast_error(v.exact, small, states)
-            lg_ok = bool(torch.isfinite(small.denoise_logits(*states[0])).all())
-        finally:
-            small.close()
-        self.verifier_check = {"verifier": "split", "err_rel_vs_fp32_mfma": c["err_rel"], "finite": c["finite"],
-                               "tolerance": self.verifier_tolerance}
-        if c["finite"] and c["err_rel"] <= self.verifier_tolerance:
-            return
-        if not lg_ok:
-            raise FloatingPointError("reference-precision engines: non-finite logits on this checkpoint (fp32 MFMA too)")
-        import warnings
-
-        warnings.warn(f"split verifier outside {self.verifier_tolerance:g} of the fp32-MFMA engine on this checkpoint "
-                      f"({c['err_rel']:.3g}, finite={c['finite']}): verifying with the fp32-MFMA engine instead",
-                      RuntimeWarning)
-        old = v.exact
-        v.exact = self._mk("exact")
-        v.exact.load_state_dict(state_dict)
-        old.close()
-        self.verifier = "exact"
-        self.verifier_check["verifier"] = "exact (fallback)"
-
     def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True):
         for k, v in state_dict.items():                         # (keys with or without 'model.module.')
             if k.rsplit(".", 1)[-1] in ("Lt_history", "Lt_count"):
                 setattr(self, k.rsplit(".", 1)[-1], torch.as_tensor(v).detach().to("cpu", torch.float32).reshape(-1).clone())
-        if self.verified is not None:
-            self.verified = self._v_fast                        # (auto may have switched to the mixed / the reference-precision engine before)
-            self.engine = self.verified.fast
-        self.engine.load_state_dict(state_dict)
-        if self.verified is not None:
-            self.verified.exact.load_state_dict(state_dict)
-            self._check_verifier(state_dict)
-            try:
-                cal = self.verified.calibrate()                 # tie_abs <- 6 x safety x measured |logits error|
-            except FloatingPointError:
-                if not self.auto:
-                    raise
-                # the fp16 engine overflows on this checkpoint (the verifier was checked finite above): auto's answer
-                cal = dict(self.verified.calibration, err_rel=float("inf"), finite=False)
-                self.verified.calibration = cal
-            if self.auto:
-                self._rung_error = {}
-                ok = cal["err_rel"] <= self.auto_tolerance       # (NaN / inf compare False)
-                self.selected_precision = "fast_verified" if ok else self.verifier
-                if not ok:
-                    for rung in self.RUNGS:
-                        if self._try_rung(rung, state_dict):
-                            self.selected_precision = rung + "_verified"
-                            break
-                    else:
-                        self.engine = self.verified.exact
-        self._report_selection()
+        selector = getattr(self, "_selector", None)
+        if selector is None:                                    # (the host half alone, without engines: the history is all it loads)
+            return self
+        sel = selector.load(state_dict)
+        self.engine, self.verified, self.selected_precision = sel.engine, sel.verified, sel.selected
+        self.verifier, self.verifier_check = sel.verifier, sel.verifier_check
+        self.selection_report = selection_report(sel, variant_name(self.pos_emb, self.timestep_type))
+        logger.info(selection_message(sel))   # one INFO record per loaded checkpoint: which engine runs, and why
         return self
-
-    RUNGS = ("hybrid", "mixed")   # auto's ladder between the fp16 engine and the reference-precision engine, fastest first
-
-    def _try_rung(self, rung: str, state_dict) -> bool:
-        """One rung of auto's ladder: the engine (built on first need; unavailable where the library has no such kernels for the model's
-        geometry) measured against the verifier exactly like the fp16 engine was; True = it is inside the tolerance and now the engine."""
-        from .verified import VerifiedGreedy
-
-        if rung not in self._v_rung:
-            try:
-                self._v_rung[rung] = VerifiedGreedy(self._mk(rung), self._v_fast.exact)
-            except RuntimeError as e:                            # (ldm_create: geometry without these kernels)
-                self._rung_error[rung] = {"unavailable": str(e)}
-                return False
-        vm = self._v_rung[rung]
-        vm.exact = self._v_fast.exact                            # (_check_verifier may have replaced the verifier engine)
-        vm.fast.load_state_dict(state_dict)
-        try:
-            cal = vm.calibrate()
-        except FloatingPointError:
-            self._rung_error[rung] = {"err_rel": float("inf"), "finite": False}
-            return False
-        self._rung_error[rung] = {"err_rel": cal["err_rel"], "err_abs": cal["err_abs"], "finite": True, "tie_abs": cal["tie_abs"]}
-        if not cal["err_rel"] <= self.auto_tolerance:
-            return False
-        self.verified = vm
-        self.engine = vm.fast
-        return True
 
     def close(self) -> None:
         """Release every engine this object built (the handles own GBs of workspace)."""
-        seen = []
-        for v in [self._v_fast] + list(self._v_rung.values()):
-            if v is not None:
-                seen += [v.fast, v.exact]
-        done = []
-        for e in seen + [self.engine]:
-            if e is not None and not any(e is d for d in done):
-                done.append(e)
-                e.close()
-
-    def _report_selection(self) -> None:
-        """One INFO record per loaded checkpoint: which engine runs, the fp16 engine's measured logits error,
-        the tolerance it was held against and the throughput class to expect — a user must be able to tell why a job runs at
-        1 200 instead of 3 900 layouts/s.  The same dictionary is `selection_report` (python -m layout_dm_amd.check_checkpoint)."""
-        sel = self.selected_precision
-        rep = {"precision_requested": self.precision, "engine_selected": sel,
-               "expected_throughput": THROUGHPUT_CLASS.get(sel, "?")}
-        if variant_name(self.pos_emb, self.timestep_type):
-            rep["denoiser_variant"] = variant_name(self.pos_emb, self.timestep_type)
-        if self.auto and self.instance_norm and not self.wide_vocab:
-            rep["reason"] = (f"timestep_type={self.timestep_type}: instance norm over a layout's rows runs on the tiled kernels of the "
-                             "reference-precision engines (split / exact) only; no fp16 engine was built or measured")
-            self.selection_report = rep
-            logger.info("layout_dm_amd: precision='auto' selected engine '%s': timestep_type=%s normalises per (layout, channel) over the "
-                        "sequence axis, which only the reference-precision engines (split / exact) serve — no fp16 engine was built; "
-                        "expect less than %s (its LayerNorm-fed GEMMs run as separate tiled launches)", sel, self.timestep_type,
-                        rep["expected_throughput"])
-            return
-        if self.verified is not None:
-            explicit = self.precision in ("mixed_verified", "hybrid_verified")
-            cal = self._v_fast.calibration if not explicit else {}
-            rep.update({"fast_logits_err_rel": cal.get("err_rel"), "fast_logits_err_abs": cal.get("err_abs"),
-                        "tolerance": self.auto_tolerance, "verifier": self.verifier, "verifier_check": dict(self.verifier_check),
-                        "tie_abs": self.verified.calibration.get("tie_abs")})
-            if explicit:
-                rep[self.precision[:-len("_verified")] + "_logits_err_rel"] = self.verified.calibration.get("err_rel")
-            for rung, err in self._rung_error.items():
-                if "unavailable" in err:
-                    rep[rung + "_unavailable"] = err["unavailable"]
-                else:
-                    rep[rung + "_logits_err_rel"] = err.get("err_rel")
-        if self.auto and self.wide_vocab:
-            rep.update({"n_class": self.num_classes, "fp16_max_classes": FP16_MAX_CLASSES,
-                        "reason": f"{self.num_classes} classes: the fp16 engines (fast / hybrid / mixed) serve at most {FP16_MAX_CLASSES}; "
-                                  "no fp16 engine was built or measured"})
-            self.selection_report = rep
-            logger.info("layout_dm_amd: precision='auto' selected engine '%s': the vocabulary has %d classes and the fp16 engines "
-                        "(fast / hybrid / mixed) serve at most %d — no fp16 engine was built; expect %s", sel, self.num_classes,
-                        FP16_MAX_CLASSES, rep["expected_throughput"])
-            return
-        self.selection_report = rep
-        if self.verified is None:
-            logger.info("layout_dm_amd: engine '%s' (as requested) — %s", sel, rep["expected_throughput"])
-            return
-        fmt = lambda e: "non-finite" if e is None or e != e or e == float("inf") else f"{e:.2e}"   # noqa: E731
-        err = rep["fast_logits_err_rel"]
-        err_s = fmt(err)
-        if self.auto:
-            why = ("inside" if sel == "fast_verified" else "OUTSIDE") + f" the {self.auto_tolerance:g} logits tolerance"
-            for rung in self.RUNGS:
-                if rung + "_logits_err_rel" in rep:
-                    why += (f"; the {rung} engine's is {fmt(rep[rung + '_logits_err_rel'])}, " + ("inside" if sel == rung + "_verified" else "OUTSIDE"))
-                elif rung + "_unavailable" in rep:
-                    why += f"; no {rung} engine for this geometry"
-            logger.info("layout_dm_amd: precision='auto' selected engine '%s': the fp16 engine's logits error on this checkpoint is %s "
-                        "(relative, against the %s reference-precision engine), %s — expect %s", sel, err_s, self.verifier, why,
-                        rep["expected_throughput"])
-        elif self.precision in ("mixed_verified", "hybrid_verified"):
-            logger.info("layout_dm_amd: engine '%s' (as requested); its logits error on this checkpoint %s (relative, against the "
-                        "%s engine) — expect %s", self.precision, fmt(rep.get(self.precision[:-len("_verified")] + "_logits_err_rel")), self.verifier,
-                        rep["expected_throughput"])
-        else:
-            logger.info("layout_dm_amd: engine '%s' (as requested); fp16 logits error on this checkpoint %s (relative, against the %s "
-                        "engine) — expect %s", sel, err_s, self.verifier, rep["expected_throughput"])
+        self._selector.close()
 
     @property
     def calibration(self) -> Dict[str, float]:
@@ -432,19 +228,12 @@ class HipMaskAndReplaceDiffusion:
         generator, so `set_seed()` (helpers/util.py:10-13) keeps runs reproducible.
         first_layout: global index of row 0 (batch sharding across calls / GPUs)."""
         eng = self.engine
-        T = self.num_timesteps
-        t_eval = int(_cfg_get(sampling_cfg, "num_timesteps", T))
-        td = float(_cfg_get(sampling_cfg, "time_difference", 0.0) or 0.0)
-        t_model, t_post = timestep_schedule(T, t_eval, td)
         if cond and cond.get("type") == "relation":
             raise NotImplementedError(
                 "cond=relation needs the relation graph (cond['batch_w_canvas']) turned into the kernel's CSR form: use "
                 "layout_dm_amd.relation.sample_with_relation, which LayoutDM.sample does (the logit adjustment of "
                 "logit_adjustment.py:88-126 then runs inside ldm_sample_loop)")
-        if seed is None:
-            # (deterministic decoding draws nothing — and must not advance torch's global generator either: the reference's argmax
-            #  path consumes no random numbers (helpers/sampling.py:110-111), and test.py's get_cond of the NEXT batch reads that stream)
-            seed = 0 if str(_cfg_get(sampling_cfg, "name")) == "deterministic" else int(torch.randint(0, 2 ** 62, (1,)).item())
+        t_model, t_post, seed = schedule_and_seed(self.num_timesteps, sampling_cfg, seed)
         B = int(batch_size)
         if B == 0:  # an empty shard (distributed.shard_range with fewer layouts than ranks)
             empty = torch.empty((0, eng.S), dtype=torch.int32, device=eng.device)

@@ -20,7 +20,7 @@ from typing import Callable, Dict, Optional
 
 import torch
 
-from .diffusion import HipMaskAndReplaceDiffusion, _cfg_get, batch_cuts, timestep_schedule
+from .diffusion import HipMaskAndReplaceDiffusion, _cfg_get, batch_cuts, schedule_and_seed
 
 
 def graph_to_csr(graph, n_graph: int, with_nodes: bool = False):
@@ -108,11 +108,7 @@ def sample_with_relation(inner: HipMaskAndReplaceDiffusion, batch_size: int, con
         # fast_verified promises the exact mode's greedy tokens; the near-tie report does not exist for the adjusted
         # steps (ldm_sample_loop refuses it), so greedy cond=relation decoding runs on the exact engine
         eng = inner.verified.exact
-    T = inner.num_timesteps
-    t_model, t_post = timestep_schedule(T, int(_cfg_get(sampling_cfg, "num_timesteps", T)),
-                                        float(_cfg_get(sampling_cfg, "time_difference", 0.0) or 0.0))
-    if seed is None:   # (deterministic decoding: no draw from torch's global generator, like the reference — diffusion.sample)
-        seed = 0 if str(_cfg_get(sampling_cfg, "name")) == "deterministic" else int(torch.randint(0, 2 ** 62, (1,)).item())
+    t_model, t_post, seed = schedule_and_seed(inner.num_timesteps, sampling_cfg, seed)
     B = int(batch_size)
     cond = dict(cond)
     for k, v in list(cond.items()):  # duplicate_cond + .to(device), base.py:321-336

@@ -11,61 +11,9 @@ import pytest
 import torch
 
 import layout_dm_amd.diffusion as D
+from _fake_engine import FakeEngine
 
 S_ATTR = 5
-
-
-class FakeEngine:
-    """binding.Engine's surface as diffusion.py / verified.py use it; logits = a fixed function of (tokens, t) plus `noise` in the
-    engines whose precision is 'fast'."""
-    fast_noise = 0.0
-    mixed_noise = 0.0
-    hybrid_noise = 1.0            # (far outside unless a test sets it)
-    mixed_available = True
-    built = []
-
-    def __init__(self, *, n_category, n_bin=32, max_elem=25, n_attr=5, n_step=100, precision="exact", max_batch=512,
-                 q_type="constrained", **_k):
-        self.q_type = q_type
-        self.S, self.C, self.T = max_elem * n_attr, n_category + 4 * n_bin + 2, n_step
-        self.n_attr, self.n_bin, self.n_category = n_attr, n_bin, n_category
-        self.pad_id, self.mask_id = self.C - 2, self.C - 1
-        self.max_batch, self.batch_round, self.precision = max_batch, 256, precision
-        self.device = torch.device("cpu")
-        if precision in ("mixed", "hybrid") and not FakeEngine.mixed_available:
-            raise RuntimeError("ldm_create: precision mixed: only the reference backbone's geometry ...")
-        FakeEngine.built.append((precision, max_batch))
-
-    def load_state_dict(self, sd):
-        pass
-
-    def _tok(self, t):
-        return torch.as_tensor(t).to(torch.int32).contiguous()
-
-    def denoise_logits(self, tokens, t):
-        tokens = self._tok(tokens)
-        assert tokens.shape[0] <= self.max_batch, f"batch {tokens.shape[0]} outside [1, max_batch = {self.max_batch}]"
-        g = torch.Generator().manual_seed(int(tokens.long().sum()) * 131 + int(t))
-        base = torch.randn(tokens.shape[0], self.S, self.C, generator=g)
-        noise = {"fast": FakeEngine.fast_noise, "mixed": FakeEngine.mixed_noise, "hybrid": FakeEngine.hybrid_noise}.get(self.precision, 0.0)
-        if noise:
-            base = base + noise * base.abs().max() * torch.sign(torch.randn(base.shape, generator=g))
-        return base
-
-    def sample_loop(self, tokens, t_model, t_post, cfg, cond=None, seed=0, first_layout=0, intermediates=False, use_graph=True,
-                    lc_keep=None, relation=None):
-        tokens = self._tok(tokens)
-        inter = torch.stack([tokens.clone() for _ in t_model]) if intermediates else None
-        return tokens, inter
-
-    def set_tie_report(self, *a, **k):
-        pass
-
-    def describe(self):
-        return {"precision": self.precision}
-
-    def close(self):
-        pass
 
 
 @pytest.fixture()
